@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- denoise-steps/sec of the MToV DDIM loop on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the K timed steps, one JSON line.
+--dump-outputs DIR also writes what the timed call returned (DIR/latents.npy, float32 [N,4,L]: every rank's latent after its
+K timed steps; the inputs are seeded, so two builds run with the same arguments can be compared output for output).
+--full adds everything else the line used to carry: the per-launch roofline, the CPU baseline, the batched / R = 64 /
+autoencoder side timings (each with its own switch below).
 
 One "step" = one B=1 UNet forward over a 16-frame 256x256 clip's tri-plane latent [1,4,2048]
 + the eta=1 DDIM update (BASELINE.json configs[1]: second-stage base UNet, 250 DDIM steps).
@@ -83,6 +89,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=250)
     ap.add_argument("--warmup", type=int, default=25)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what is not the headline figure: per-launch roofline and kernel families, the CPU "
+                         "baseline, batched clips, R = 64, the autoencoder (--no-cpu-baseline, --cpu-*, --profile-iters, --batched-clips, "
+                         "--no-autoencoder and --no-res64 select among these legs and mean nothing without --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed call returned to DIR/latents.npy: float32 [n_gpus,4,L], each rank's latent after its timed steps")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=10, help="timed oracle steps for the cpu_baseline leg")
     ap.add_argument("--cpu-physical-probe", action="store_true",
@@ -102,6 +114,8 @@ def main():
     ap.add_argument("--res", type=int, default=32, choices=(32, 64),
                     help="latent resolution R: 32 = BASELINE configs[1] (the metric's workload), 64 = configs[3] (512x512 clip)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import ctypes as C
     import torch.distributed as dist
@@ -216,15 +230,15 @@ def main():
     dt = float(tmax.item())
     gpu_sections["timed_steps"] = dt
     assert torch.isfinite(xt).all()
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds now: the latent the sampler call left in place (with N > 1 ranks: the gathered ones)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        lat = torch.cat(out) if use_dist else xt
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), lat.detach().to("cpu", torch.float32).numpy())
 
-    result = None
-    if rank == 0 and dry:
-        result = {"metric": "DRY RUN of bench.py's distributed scaffolding (gloo, CPU, stub sampler) -- not a measurement", "dry_run": True,
-                  "value": round(world * K / dt, 3), "unit": "stub-steps/s", "n_gpus": world, "steps": K, "warmup": W,
-                  "ms_per_step": round(1e3 * dt / K, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-                  "data": "none (stub)", "distributed": dist_info, "config": {"workload": "dry run", "clips": world}}
-    elif rank == 0:
-        work = um.work(dev)
+    def full_report(result):
+        """--full: everything in the line beyond the headline figure (runs of their own after the timed region; rank 0 only)."""
         # ---- roofline of the dominant kernel family, measured live with hipEvents around every launch
         t_sec = time.perf_counter()
         prof = um.profile_forward(1, args.profile_iters, dev, step=True)   # the launches of one SAMPLER step
@@ -564,6 +578,28 @@ def main():
         attn_roof["frac"] = round(attn_roof["achieved"] / MFMA_F32_PEAK_TF, 4)
         attn_roof["mfma_util_counter"] = pmc.get("k_attention", {}).get("mfma_util")   # matrix-pipe busy fraction from SQ counters (committed pass)
         attn_roof["counter_kind"] = "committed" if attn_roof["mfma_util_counter"] is not None else None
+        result.update({
+            "roofline": roofline,
+            # wall seconds of the sections of this process in which the GPU works (a utilisation sampler with a 1 Hz cadence sees little of
+            # them next to the CPU-baseline leg, which keeps the GPU idle for tens of seconds)
+            "gpu_active_s": {"total": round(sum(gpu_sections.values()), 3), **{k: round(v, 3) for k, v in gpu_sections.items()}},
+            "cpu_baseline": cpu,
+            "step_ms_sum_of_launches": round(step_ms_events, 4),
+            "families": families,
+            "roofline_attention": attn_roof,
+            "batched_info": batched,
+            "res64_info": res64,
+            "autoencoder_info": ae_info,
+        })
+
+    result = None
+    if rank == 0 and dry:
+        result = {"metric": "DRY RUN of bench.py's distributed scaffolding (gloo, CPU, stub sampler) -- not a measurement", "dry_run": True,
+                  "value": round(world * K / dt, 3), "unit": "stub-steps/s", "n_gpus": world, "steps": K, "warmup": W,
+                  "ms_per_step": round(1e3 * dt / K, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+                  "data": "none (stub)", "distributed": dist_info, "config": {"workload": "dry run", "clips": world}}
+    elif rank == 0:
+        work = um.work(dev)
         result = {
             "metric": f"denoise-steps/sec (16-frame {8 * R}^2 clip, 250 DDIM steps)",
             "value": round(world * K / dt, 3),
@@ -589,20 +625,13 @@ def main():
             "config": {"workload": f"configs[{1 if R == 32 else 3}]: 16-frame {8 * R}x{8 * R} clip = tri-plane latent [1,4,{L}] (R={R},T=16), "
                                    "base second-stage UNet (132.2M live params), DDIM eta=1, 250-step schedule, B=1 per GPU",
                        "clips": world, "parallelism": f"clip-sharded x{world}, all_gather of latents at the end"},
-            "roofline": roofline,
-            # wall seconds of the sections of this process in which the GPU works (a utilisation sampler with a 1 Hz cadence sees little of
-            # them next to the CPU-baseline leg, which keeps the GPU idle for tens of seconds)
+            "full": args.full,
             "gpu_active_s": {"total": round(sum(gpu_sections.values()), 3), **{k: round(v, 3) for k, v in gpu_sections.items()}},
-            "cpu_baseline": cpu,
-            "step_ms_sum_of_launches": round(step_ms_events, 4),
             "launches_per_step": work["n_launches_step"],
             "flops_per_step": {k: work[k] for k in ("flops_conv3x3", "flops_1x1", "flops_attn_core", "flops_linear")},
-            "families": families,
-            "roofline_attention": attn_roof,
-            "batched_info": batched,
-            "res64_info": res64,
-            "autoencoder_info": ae_info,
         }
+        if args.full:
+            full_report(result)
     barrier()
     if use_dist:
         dist.destroy_process_group()

@@ -74,17 +74,20 @@ def test_sharded_sampling_gloo_world8_eight_clips_mirrors_configs2():
     assert all(calls == [r] for r, _, calls in res)                     # clip i ran on rank i and nowhere else
 
 
-def test_bench_py_eight_rank_dry_run_under_gloo():
+def test_bench_py_eight_rank_dry_run_under_gloo(tmp_path):
     """bench.py --gpus 8 with MTV_BENCH_DRYRUN=1: eight processes under torch.distributed.run, gloo instead of RCCL, the sampler call
     replaced by a stub (no GPU here) -- everything else is bench.py's own N > 1 path: rendezvous from the env, barrier-bracketed timed
-    region, per-rank step times gathered, the final all_gather of the latents, MAX over ranks, ONE JSON line on rank 0."""
+    region, per-rank step times gathered, the final all_gather of the latents, MAX over ranks, ONE JSON line on rank 0, and
+    --dump-outputs: rank 0 writes the gathered latents."""
     import json
     import subprocess
     import sys
+    import numpy as np
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MTV_BENCH_DRYRUN="1", OMP_NUM_THREADS="1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-                        "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "6", "--warmup", "2"],
+                        "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "6", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path / "dump")],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -96,6 +99,10 @@ def test_bench_py_eight_rank_dry_run_under_gloo():
     pr = di["per_rank_ms_per_step"]
     assert 0 < pr["min"] <= pr["median"] <= pr["max"] <= d["ms_per_step"] * 1.001
     assert abs(d["value"] - 8 * 6 / (d["ms_per_step"] * 6e-3)) <= 1e-2 * d["value"]      # whole-job aggregate: N K / max-over-ranks time
+    assert sorted(os.listdir(tmp_path / "dump")) == ["latents.npy"]
+    lat = np.load(tmp_path / "dump" / "latents.npy")
+    assert lat.dtype == np.float32 and lat.shape == (8, 4, 2048) and np.isfinite(lat).all()
+    assert len({lat[r].tobytes() for r in range(8)}) == 8                               # one latent per rank (each rank seeds its own clip)
 
 
 def test_without_process_group_is_a_plain_loop():
@@ -212,17 +219,20 @@ def test_rccl_world1_real_sampler_matches_unsharded():
 
 
 @pytest.mark.gpu
-def test_bench_py_distributed_path_single_rank():
+def test_bench_py_distributed_path_single_rank(tmp_path):
     """bench.py's own N > 1 code path (RCCL init, per-rank timing gather, final all_gather of the latents, NUMA binding),
     exercised as far as one GPU allows: MTV_BENCH_FORCE_DIST=1 runs it with a world of one rank.  The driver's 8-GPU
-    scaling run then only adds ranks."""
+    scaling run then only adds ranks.  A plain run (no --full): the line carries the headline figure and none of the side legs,
+    and --dump-outputs writes the latent the timed call returned."""
     import json
     import subprocess
     import sys
+    import numpy as np
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MTV_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "2", "--ramp-steps", "10",
-                        "--no-cpu-baseline", "--batched-clips", "0", "--no-autoencoder", "--profile-iters", "1"],
+                        "--no-cpu-baseline", "--batched-clips", "0", "--no-autoencoder", "--profile-iters", "1",
+                        "--dump-outputs", str(tmp_path)],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -232,3 +242,6 @@ def test_bench_py_distributed_path_single_rank():
     assert di["backend"] == "nccl" and di["world_size_reported"] == 1 and di["latents_gathered"] == 1
     assert 0 < di["per_rank_ms_per_step"]["min"] <= di["per_rank_ms_per_step"]["max"] <= d["ms_per_step"] * 1.001
     assert di["gather_and_barrier_ms"] >= 0 and "cpu_affinity" in d and "steps_sampled" in d
+    assert d["full"] is False and not {"roofline", "cpu_baseline", "batched_info", "res64_info", "autoencoder_info"} & set(d)
+    lat = np.load(tmp_path / "latents.npy")
+    assert lat.dtype == np.float32 and lat.shape == (1, 4, 2048) and np.isfinite(lat).all() and np.abs(lat).max() > 0

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 for r in $(seq 1 $R); do
     for lab in a b; do
         if [ $lab = a ]; then E=$A; else E=$B; fi
-        env $E python bench.py --steps 250 --warmup 25 --no-cpu-baseline 2>/dev/null | tail -1 > /tmp/ab_line.json
+        env $E python bench.py --full --steps 250 --warmup 25 --no-cpu-baseline 2>/dev/null | tail -1 > /tmp/ab_line.json
         python - $lab $r >> $O <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab_line.json").read())

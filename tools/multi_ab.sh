@@ -9,7 +9,7 @@ for r in $(seq 1 $R); do
     k=0
     for E in "$@"; do
         k=$((k + 1))
-        env $E python bench.py --steps 250 --warmup 25 --no-cpu-baseline --no-autoencoder --no-res64 --batched-clips 0 2>/dev/null | tail -1 > /tmp/ab_line.json
+        env $E python bench.py --full --steps 250 --warmup 25 --no-cpu-baseline --no-autoencoder --no-res64 --batched-clips 0 2>/dev/null | tail -1 > /tmp/ab_line.json
         python - $k $r >> $O <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab_line.json").read())
