@@ -221,6 +221,15 @@ int mtv_debug_deep(int mode);
 #define MTV_DEEP_OPT_BLOCK_ALL 32
 #define MTV_DEEP_OPT_FIN_PASS 64
 int mtv_debug_deep_options(int mask);
+/* Form of the fused attention + proj_out kernel (k_deep_attn) in plans built after this call.  Environment, read once per process:
+ *   MTV_DEEP_ATTN_QT=2    two query tiles x four key parts per workgroup (round 4) instead of one x eight; implies head groups (below);
+ *   MTV_DEEP_ATTN_HPW=2   head groups everywhere (round 6: at [128 x 512] two heads per workgroup, 64-column proj slices, four output slabs);
+ *                         unset: ONE head per workgroup with 128-column proj slices (one output slab per head) at the 128-token blocks of
+ *                         64-wide heads, head groups elsewhere.
+ * This call overrides MTV_DEEP_ATTN_HPW: 1 = one head per workgroup wherever that form exists (C a multiple of 128, at most 8 heads, a
+ * power of two), 2 = head groups everywhere, -1 = back to the environment / the rule.  Either way the proj_out slice of a workgroup comes
+ * from the lane-linear copy of the matrix (the one k_conv_pw reads) straight into MFMA operand registers. */
+int mtv_debug_deep_attn_form(int form);
 
 /* 0: replay the step as a hipGraph (default); 1: plain launches (profiling / debugging). */
 int mtv_set_eager(mtv_ctx* ctx, int eager);

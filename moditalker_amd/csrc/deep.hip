@@ -818,6 +818,8 @@ __device__ __forceinline__ float deep_swap_max32(float x) {
 // lane COLUMN: softmax reductions are register values + two lane swaps; the P^T registers are the B operand of
 // O^T += V^T P^T, as in k_attention), the four key parts of a query tile are merged through LDS into the normalised output
 // rows.  Then D = attention rows x Wp[head group rows][column group] on the same MFMA, K split over the waves, summed in LDS.
+// With the packed matrix (DeepAttnArgs::Wpk) the B fragments of a wave's proj tile are requested at kernel entry and stay in registers; with HPW = 1 / NC = 128 (round 7:
+// the [128 x 512] d = 64 blocks) a wave owns a whole tile and stores its output quads from the accumulators (profiles/r07_deep_attn_heads.md).
 template <int D>
 __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
     const int tid = threadIdx.x;
@@ -862,24 +864,40 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
     float* const Vt = Ks + a.kcap * KSTR;                     // [D][VSTR]
     float* const Qs = Vt + D * VSTR;                          // [QR][KSTR]
     float* const Att = Qs + QR * KSTR;                        // [QR][AS]: normalised attention rows of the head group
+    // packed weights (DeepAttnArgs::Wpk): no Wt.  kparts == 1 (NC = 128: launch_deep_attn admits it with packed weights only): every wave owns a whole proj tile -- no
+    // cross-wave sum, the epilogue runs from the accumulators, the completion scratch gets LDS of its own (it is written before the first barrier)
+    const bool pk = a.Wpk != nullptr;
     float* const Wt = Att + QR * AS;                          // [NC][WS]: proj slice, transposed (k contiguous)
-    float* const Os = Wt + NC * WS;                           // [8 waves][16 queries][D + 4]: key-part partials (then proj partials)
+    float* const Os = Wt + (pk ? 0 : NC * WS);                // [8 waves][16 queries][D + 4]: key-part partials (then proj partials)
     constexpr int OSF = 8 * 16 * (D + 4) > 8 * 16 * 20 + DEEP_FIN_FLOATS ? 8 * 16 * (D + 4) : 8 * 16 * 20 + DEEP_FIN_FLOATS;
     float* const ml = Os + OSF;                               // [8 waves][16 queries][2]: (m, l) of the key parts
     const int qt = QT == 2 ? (wave & 1) : 0, kp = QT == 2 ? (wave >> 1) : wave;      // this wave: query tile, key part
     const int KPS = 8 / QT;                                   // key parts (= the stride of a wave's key tiles)
-    // ---- proj slice requested first: it depends on nothing (held in registers until the first barrier)
-    const int kw = HPW * D, wq = NC >> 2;                     // K rows of the slice, column quads
-    f32x4 wreg[4];                                            // (NC = 64: up to four quads per thread)
+    // proj phase: [QR rows][NC cols] = Att [QR][kw] x Wp slice; wave -> (tile, K part)
+    // (NC = 16 .. 128 and QT = 1 | 2 are powers of two -- launch_deep_attn -- and so is everything derived from them: shifts, not divisions, on the way to the first request)
+    const int kw = HPW * D, wq = NC >> 2, wq_sh = __builtin_ctz(wq);   // K rows of the slice, column quads
+    const int nct = NC >> 4, ntile = QT * nct, nt_sh = __builtin_ctz(ntile), kparts = 8 >> nt_sh;      // (ntile 1, 2, 4 or 8)
+    const int tile = wave & (ntile - 1), kpart = wave >> nt_sh;
+    const int rt = QT == 2 ? (tile & 1) : 0, ct = QT == 2 ? (tile >> 1) : tile;
+    const int kchunks = kw >> 4, cpp = (kchunks + kparts - 1) >> (3 - nt_sh);  // 16-channel chunks per K part (packed: <= 4)
+    const bool direct = kparts == 1;
+    float* const fscratch = direct ? ml + 8 * 16 * 2 : Os + 8 * 16 * 20;     // completion scratch (not direct: past the proj partials -- the key-part partials that lay there are dead by then)
+    // ---- proj slice requested first: it depends on nothing (held in registers until the first barrier; packed: until the proj phase)
+    f32x4 wreg[4];                                            // (NC = 64: up to four quads per thread; packed: the B fragments of up to four chunks)
     const int wu_n = (kw * wq + DEEP_NTH - 1) / DEEP_NTH;     // (uniform)
     {
+        // Four loads per thread in either form, the ADDRESS chosen by the form -- no branch, no fill value: a register that one path loads and another path writes makes
+        // the compiler wait for the load at the join, i.e. before K / V are requested.  Slots a form does not use re-read a valid quad and are never consumed.
+        // packed: lane (j, g) of (column block, chunk) holds Wp[16 chunk + 4 g .. + 3][16 block + j] -- 1 KB per wave instruction
+        const float* wpb = a.Wpk + (((size_t)(cg * nct + ct) * (C >> 4) + hg * kchunks + (kpart * cpp < kchunks ? kpart * cpp : 0)) * 64 + lane) * 4;
         const float* wb = a.Wp + (size_t)(hg * kw) * a.ldw + cg * NC;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int e = tid + DEEP_NTH * u;
-            const int kr = e / wq, cq = e - kr * wq;
-            if (u < 2 || u < wu_n) wreg[u] = *reinterpret_cast<const f32x4*>(wb + (size_t)(kr < kw ? kr : 0) * a.ldw + 4 * cq);
-            else wreg[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const int kr = e >> wq_sh, cq = e & (wq - 1);
+            const float* ps = wb + (size_t)(kr < kw ? kr : 0) * a.ldw + 4 * cq;
+            const float* pp = wpb + ((u < cpp && kpart * cpp + u < kchunks) ? u : 0) * 256;
+            wreg[u] = *reinterpret_cast<const f32x4*>(pk ? pp : ps);
         }
     }
     // epilogue operands of head group 0 (bias + the block's input as residual): requested now, they land under the attention
@@ -887,9 +905,11 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
     const int nq4 = NC >> 2;
     // (RAW registers, added up in the epilogue: using a loaded value here would make the wave wait before it requests K / V)
     f32x4 pre_b = {0.f, 0.f, 0.f, 0.f}, pre_r = {0.f, 0.f, 0.f, 0.f};
-    const bool pre_ok = hg == 0 && tid < QR * nq4 && q0 + tid / nq4 < L;
+    // this thread's output quad (row, first column): direct form -- the one its accumulator holds (D^T: lane (j, g) = query j, columns 4 g .. + 3 of the wave's tile)
+    const int own_r = direct ? j : tid >> wq_sh, own_c = direct ? 16 * ct + 4 * g : 4 * (tid & (nq4 - 1));
+    const bool pre_ok = hg == 0 && tid < QR * nq4 && q0 + own_r < L;
     if (pre_ok) {
-        const int rr = tid / nq4, n = cg * NC + 4 * (tid - rr * nq4);
+        const int rr = own_r, n = cg * NC + own_c;
         pre_b = *reinterpret_cast<const f32x4*>(a.bias + n);
         pre_r = *reinterpret_cast<const f32x4*>(a.res.p + ((size_t)b * L + q0 + rr) * a.res.C + n);      // slab 0; further slabs in the epilogue
     }
@@ -941,11 +961,18 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
         if (hh == 0) DEEP_STAMP(2);
         if (hh == 1) DEEP_STAMP(10);
         if (hh + 1 < HPW) issue(hh + 1);
-        if (hh == 0) {
+        if (hh == 0 && direct && tg) {                       // (the ticket was requested before K / V: it has landed with them)
+            if (tid == 0) *reinterpret_cast<unsigned*>(fscratch) = (unsigned)(early >> __builtin_ctz(a.nhg)) + 1u;
+            if (hg == 0) {
+                double* st = reinterpret_cast<double*>(fscratch + 4);
+                for (int e = tid; e < a.fin.nstat * 96 * 2; e += DEEP_NTH) st[e] = 0.0;
+            }
+        }
+        if (hh == 0 && !pk) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int e = tid + DEEP_NTH * u;
-                const int kr = e / wq, cq = e - kr * wq;
+                const int kr = e >> wq_sh, cq = e & (wq - 1);
                 if (kr < kw && (u < 2 || u < wu_n)) {
                     const int krs = kr ^ (((cq >> 1) & wswz) << 2);              // (the V^T swizzle, for the same transposing store: row stride = 4 mod 32)
 #pragma unroll
@@ -1057,45 +1084,48 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
         __syncthreads();
     }
     DEEP_STAMP(6);
-    // ---- proj: [QR rows][NC cols] = Att [QR][kw] x Wt^T; wave -> (tile, K part)
-    const int nct = NC >> 4, ntile = QT * nct, kparts = 8 / ntile;      // (ntile 1, 2 or 4)
-    const int tile = wave % ntile, kpart = wave / ntile;
-    const int rt = QT == 2 ? (tile & 1) : 0, ct = QT == 2 ? (tile >> 1) : tile;
-    const int kchunks = kw >> 4, cpp = (kchunks + kparts - 1) / kparts;  // 16-channel chunks per K part
+    // ---- proj: [QR rows][NC cols] = Att [QR][kw] x Wp slice (tile / K part of this wave: above)
     f32x4 pacc = {0.f, 0.f, 0.f, 0.f};
-    for (int cc = kpart * cpp; cc < (kpart + 1) * cpp && cc < kchunks; ++cc) {
-        const f32x4 af = *reinterpret_cast<const f32x4*>(Att + (16 * rt + j) * AS + 16 * cc + 4 * g);
-        const f32x4 bf = *reinterpret_cast<const f32x4*>(Wt + (16 * ct + j) * WS + 4 * ((4 * cc + g) ^ ((2 * ct + (j >> 3)) & wswz)));
+    if (pk) {
 #pragma unroll
-        for (int sI = 0; sI < 4; ++sI) pacc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[sI], bf[sI], pacc, 0, 0, 0);
-    }
-    {   // D lane (col j, group g) reg r = row 4 g + r -> [wave][row][col]
-        float* pp = Os + (size_t)wave * 16 * 20 + (4 * g) * 20 + j;
+        for (int u = 0; u < 4; ++u) {
+            const int cc = kpart * cpp + u;
+            if (u < cpp && cc < kchunks) {                      // (uniform)
+                const f32x4 af = *reinterpret_cast<const f32x4*>(Att + (16 * rt + j) * AS + 16 * cc + 4 * g);
+                // direct: operands swapped -> D^T, lane (query j, group g) holds columns 4 g .. + 3 of the tile: one output quad per lane, no trip through LDS
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr) pp[rr * 20] = pacc[rr];
+                for (int sI = 0; sI < 4; ++sI)
+                    pacc = direct ? __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[u][sI], af[sI], pacc, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x4f32(af[sI], wreg[u][sI], pacc, 0, 0, 0);
+            }
+        }
+    } else {
+        for (int cc = kpart * cpp; cc < (kpart + 1) * cpp && cc < kchunks; ++cc) {
+            const f32x4 af = *reinterpret_cast<const f32x4*>(Att + (16 * rt + j) * AS + 16 * cc + 4 * g);
+            const f32x4 bf = *reinterpret_cast<const f32x4*>(Wt + (16 * ct + j) * WS + 4 * ((4 * cc + g) ^ ((2 * ct + (j >> 3)) & wswz)));
+#pragma unroll
+            for (int sI = 0; sI < 4; ++sI) pacc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[sI], bf[sI], pacc, 0, 0, 0);
+        }
     }
-    float* const fscratch = Os + 8 * 16 * 20;                // past the proj partials (the key-part partials that lay here are dead)
-    if (tg && tid == 0) *reinterpret_cast<unsigned*>(fscratch) = (unsigned)(early >> __builtin_ctz(a.nhg)) + 1u;
-    if (tg && hg == 0) {
-        double* st = reinterpret_cast<double*>(fscratch + 4);
-        for (int e = tid; e < a.fin.nstat * 96 * 2; e += DEEP_NTH) st[e] = 0.0;
+    if (!direct) {
+        {   // D lane (col j, group g) reg r = row 4 g + r -> [wave][row][col]
+            float* pp = Os + (size_t)wave * 16 * 20 + (4 * g) * 20 + j;
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) pp[rr * 20] = pacc[rr];
+        }
+        if (tg && tid == 0) *reinterpret_cast<unsigned*>(fscratch) = (unsigned)(early >> __builtin_ctz(a.nhg)) + 1u;
+        if (tg && hg == 0) {
+            double* st = reinterpret_cast<double*>(fscratch + 4);
+            for (int e = tid; e < a.fin.nstat * 96 * 2; e += DEEP_NTH) st[e] = 0.0;
+        }
+        __syncthreads();
     }
-    __syncthreads();
     DEEP_STAMP(7);
     const unsigned epoch = tg ? *reinterpret_cast<const unsigned*>(fscratch) : 0u;
     const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(a.fin.gran, 0, tg ? (int)a.fin.gran_bytes : 0, 0x00020000);
     const unsigned slice_gran = (unsigned)((size_t)a.B * L * C);
-    // epilogue: thread -> (row, column quad); K parts summed in order; head group 0 adds bias + residual
-    for (int e = tid; e < QR * (NC >> 2); e += DEEP_NTH) {
-        const int rr = e / (NC >> 2), cq = e - rr * (NC >> 2);
-        const int tok = q0 + rr;
-        if (tok >= L) continue;
-        const int t2 = (rr >> 4) + QT * ((4 * cq) >> 4);       // tile of this quad
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        for (int k2 = 0; k2 < kparts; ++k2)
-            v += *reinterpret_cast<const f32x4*>(Os + (size_t)(t2 + ntile * k2) * 16 * 20 + (rr & 15) * 20 + ((4 * cq) & 15));
-        const int n = cg * NC + 4 * cq;
-        if (hg == 0) {                                          // (e == tid: 32 NC / 4 <= 512 quads, one per thread)
+    // epilogue of one output quad (row tok, columns n .. n + 3): head group 0 adds bias + residual
+    auto emit = [&](int tok, int n, f32x4 v) {
+        if (hg == 0) {                                          // (one quad per thread: the one pre_b / pre_r were requested for)
             v += pre_b + pre_r;
             for (int k2 = 1; k2 < a.res.ks; ++k2) v += *reinterpret_cast<const f32x4*>(a.res.p + (size_t)k2 * a.res.slab_stride + ((size_t)b * L + tok) * a.res.C + n);
         }
@@ -1112,11 +1142,26 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
                 deep_fin_stat(a.fin, fscratch, tok, n, v);
             }
         }
+    };
+    if (direct) {
+        if (q0 + own_r < L) emit(q0 + own_r, cg * NC + own_c, pacc);
+    } else {
+        // thread -> (row, column quad); K parts summed in order
+        for (int e = tid; e < QR * (NC >> 2); e += DEEP_NTH) {
+            const int rr = e / (NC >> 2), cq = e - rr * (NC >> 2);
+            const int tok = q0 + rr;
+            if (tok >= L) continue;
+            const int t2 = (rr >> 4) + QT * ((4 * cq) >> 4);       // tile of this quad
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            for (int k2 = 0; k2 < kparts; ++k2)
+                v += *reinterpret_cast<const f32x4*>(Os + (size_t)(t2 + ntile * k2) * 16 * 20 + (rr & 15) * 20 + ((4 * cq) & 15));
+            emit(tok, cg * NC + 4 * cq, v);                         // (e == tid: 32 NC / 4 <= 512 quads)
+        }
     }
     if (tg && hg == 0) deep_fin_flush(a.fin, fscratch, b, tid);
     if (a.fin.out && !tg) {
         // ---- in-launch completion over the head groups (the K slices of the projection)
-        float* scratch = Os + 8 * 16 * 20;                       // past the proj partials
+        float* scratch = fscratch;
         if (deep_fin_arrive(a.fin, (b * a.nqg + qg) * a.ncg + cg, a.nhg, scratch, tid)) {
             for (int e = tid; e < QR * (NC >> 2); e += DEEP_NTH) {
                 const int rr = e / (NC >> 2), cq = e - rr * (NC >> 2);
@@ -2110,11 +2155,15 @@ hipError_t launch_deep_repack(const float* W, int ldw, float* dst, const DeepArg
 }
 
 
-static size_t deep_attn_smem(const DeepAttnArgs& a, int D) {
+// (with_wt: the size with the transposed proj slice even where packed weights make it unnecessary -- deep_attn_configure's choice among the older forms
+// must not depend on whether the caller has a packed copy)
+static size_t deep_attn_smem(const DeepAttnArgs& a, int D, bool with_wt = false) {
     const int KSTR = D + 4, VSTR = a.kcap + 4, AS = a.HPW * D + 8, WS = a.HPW * D + 4;
     const int os = 8 * 16 * (D + 4) > 8 * 16 * 20 + DEEP_FIN_FLOATS ? 8 * 16 * (D + 4) : 8 * 16 * 20 + DEEP_FIN_FLOATS;   // key-part partials | proj partials + completion scratch
     const int QR = 16 * (a.QT == 1 ? 1 : 2);
-    return (size_t)(a.kcap * KSTR + D * VSTR + QR * KSTR + QR * AS + a.NC * WS + os + 8 * 16 * 2) * 4;
+    const int wt = (a.Wpk && !with_wt) ? 0 : a.NC * WS;
+    const int fsc = a.NC == 128 ? DEEP_FIN_FLOATS : 0;       // one tile per wave: completion scratch of its own
+    return (size_t)(a.kcap * KSTR + D * VSTR + QR * KSTR + QR * AS + wt + os + 8 * 16 * 2 + fsc) * 4;
 }
 
 bool deep_attn_configure(DeepAttnArgs& a) {
@@ -2128,6 +2177,19 @@ bool deep_attn_configure(DeepAttnArgs& a) {
     static const int env_qt = getenv("MTV_DEEP_ATTN_QT") ? atoi(getenv("MTV_DEEP_ATTN_QT")) : 1;
     a.QT = env_qt == 2 ? 2 : 1;
     a.nqg = (a.L + 16 * a.QT - 1) / (16 * a.QT);
+    // ONE head per workgroup, 128-column proj slices from the packed matrix (HPW = 1, NC = 128; QT = 1 only): at [128 x 512] d = 64 8 query groups x 8 head groups x 4
+    // column groups = the same 256 workgroups, each loading ONE head's K / V (64 KB instead of 128) and the attention of a (head, query tile) computed 4 times instead of
+    // 8; every wave owns one 16-column proj tile over the whole K slice.  Twice the output slabs (H of them) for the consumers to add.  The rule takes it where the step
+    // was measured with it: 128-token blocks of 64-wide heads whose workgroups are all resident together (profiles/r07_deep_attn_heads.md).
+    // MTV_DEEP_ATTN_HPW=2 (or form 2): never; form 1: wherever the form exists.
+    static const int env_hpw = getenv("MTV_DEEP_ATTN_HPW") ? atoi(getenv("MTV_DEEP_ATTN_HPW")) : 0;
+    const int form = a.form ? a.form : (env_hpw == 2 ? 2 : 0);
+    if (form != 2 && a.QT == 1 && a.Wpk && a.C % 128 == 0 && a.H <= 8 && !(a.H & (a.H - 1))) {
+        a.HPW = 1; a.NC = 128; a.nhg = a.H; a.ncg = a.C / 128;
+        const long wgs = (long)a.B * a.nqg * a.nhg * a.ncg;
+        const bool rule = d == 64 && a.L > 112 && a.H == 8 && wgs >= 128 && wgs <= 256;
+        if ((form == 1 || rule) && deep_attn_smem(a, d) <= 160 * 1024) return true;
+    }
     // head group = K slice of the projection = an output slab: as few slabs as the grid allows (consumers re-read every slab)
     for (int hpw : {8, 4, 2, 1}) {
         if (a.H % hpw || hpw * d > 128) continue;
@@ -2136,7 +2198,7 @@ bool deep_attn_configure(DeepAttnArgs& a) {
             if ((hpw * d) * (nc / 4) > (nc == 64 ? 4 : 2) * DEEP_NTH) continue;             // proj slice: two (NC = 64: four) 16-byte quads per thread
             a.HPW = hpw; a.NC = nc; a.nhg = a.H / hpw; a.ncg = a.C / nc;
             if (a.nhg > 8 || (a.nhg & (a.nhg - 1))) continue;
-            if (deep_attn_smem(a, d) > 160 * 1024) continue;
+            if (deep_attn_smem(a, d, true) > 160 * 1024) continue;
             const long wgs = (long)a.B * a.nqg * a.nhg * a.ncg;
             if (wgs >= 128) return true;                                     // enough to occupy half the chip: take the fewest slabs
         }
@@ -2146,7 +2208,7 @@ bool deep_attn_configure(DeepAttnArgs& a) {
         if (a.H % hpw || hpw * d > 128) continue;
         a.HPW = hpw; a.NC = 16; a.nhg = a.H / hpw; a.ncg = a.C / 16;
         if (a.nhg > 8 || (a.nhg & (a.nhg - 1)) || (hpw * d) * 4 > 2 * DEEP_NTH) continue;
-        if (deep_attn_smem(a, d) <= 160 * 1024) return true;
+        if (deep_attn_smem(a, d, true) <= 160 * 1024) return true;
     }
     return false;
 }
@@ -2156,9 +2218,16 @@ hipError_t launch_deep_attn(const DeepAttnArgs& a0, hipStream_t s) {
     const int d = a.C / a.H;
     a.nslots = a.B * a.nqg * a.nhg;
     a.inv_nslots = 1.0f / (float)a.nslots;
-    const size_t smem = deep_attn_smem(a, d);
     if (a.QT != 1 && a.QT != 2) return hipErrorInvalidValue;
-    if (smem > 160 * 1024 || (a.NC != 16 && a.NC != 32 && !(a.NC == 64 && a.QT == 1)) || !(a.res.ks >= 1 && a.res.ks <= 8)) return hipErrorInvalidValue;
+    const bool h1 = a.NC == 128;                             // one proj tile per wave: packed weights, one query tile, the K slice in four chunks at most
+    if (h1 && !(a.QT == 1 && a.HPW == 1 && a.Wpk && d <= 64 && a.C % 128 == 0)) return hipErrorInvalidValue;
+    if (!h1 && a.NC != 16 && a.NC != 32 && !(a.NC == 64 && a.QT == 1)) return hipErrorInvalidValue;
+    {   // packed B fragments live in four registers quads per lane: chunks per K part <= 4 (every form deep_attn_configure makes), else the LDS-staged slice
+        const int kparts = 8 / (a.QT * (a.NC >> 4)), kchunks = (a.HPW * d) >> 4;
+        if ((a.C & 15) || (kchunks + kparts - 1) / kparts > 4) { if (h1) return hipErrorInvalidValue; a.Wpk = nullptr; }
+    }
+    const size_t smem = deep_attn_smem(a, d);
+    if (smem > 160 * 1024 || !(a.res.ks >= 1 && a.res.ks <= 8)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(a.ncg * a.nslots));
     if (d == 16) hipLaunchKernelGGL((k_deep_attn<16>), grid, dim3(DEEP_NTH), smem, s, a);
     else if (d == 32) hipLaunchKernelGGL((k_deep_attn<32>), grid, dim3(DEEP_NTH), smem, s, a);

@@ -380,11 +380,16 @@ struct DeepAttnArgs {
     float scale;             // d^-1/4, applied to q and to k
     const float* Wp;         // proj_out as k_conv stores it: [C rows = input channel][ldw], columns = output channel
     int ldw;
+    const float* Wpk;        // the same matrix lane-linear (ConvArgs::Wpk layout, [C / 16][C / 16][64 lanes][4]), or null: with it a wave reads the B fragments of its
+                             // proj tile straight into registers at kernel entry and the transposed LDS copy of the slice (Wt) is not built
+    int form;                // input of deep_attn_configure: 0 = the rule (MTV_DEEP_ATTN_HPW / MTV_DEEP_ATTN_QT), 1 = one head per workgroup with 128-column
+                             // proj slices wherever that form exists (else the rule), 2 = never that form
     const float* bias;       // [C]
     DeepSrc res;             // the block's input x (residual), possibly slabs
     float* out;              // slab 0 of [H / HPW][B][L][C]
     unsigned out_slab_stride;
-    int HPW, NC;             // heads per workgroup (K slice = HPW d channels), output columns per workgroup (16 or 32; 64 with QT = 1)
+    int HPW, NC;             // heads per workgroup (K slice = HPW d channels), output columns per workgroup (16 or 32; 64 with QT = 1; 128 with QT = 1, HPW = 1
+                             // and packed weights: every wave owns one 16-column tile over the whole K slice, no cross-wave sum)
     int nhg, nqg, ncg;       // head groups, query groups (16 QT rows), column groups
     int QT;                  // query tiles (16 rows) per workgroup: 2 = 2 query tiles x 4 key parts (round 4), 1 = 1 query tile x 8 key parts (round 6: half the
                              // recomputed attention per workgroup, 64-column proj slices)

@@ -200,6 +200,7 @@ static bool table_matches_formula(const std::vector<int>& h, int ntaps, bool upm
 // =====================================================================================
 static int g_deep_mode = -1;       // mtv_debug_deep: -1 = MTV_DEEP / default (on), 0 = every conv on k_conv, 1 = on
 static int g_resident_override = 0; // mtv_debug_resident_cus: > 0 = contexts created afterwards plan for that many co-resident CUs
+static int g_deep_attn_form = -1;  // mtv_debug_deep_attn_form: -1 / 0 = deep_attn_configure's rule (MTV_DEEP_ATTN_HPW), 1 / 2 = DeepAttnArgs::form
 static int g_deep_opts = -1;       // mtv_debug_deep_options: -1 = the MTV_DEEP_* environment / defaults, else a bit mask (MTV_DEEP_OPT_*)
 static bool deep_opt(int bit, const char* env, bool dflt) {
     if (g_deep_opts >= 0) return (g_deep_opts & bit) != 0;
@@ -790,6 +791,8 @@ struct Builder {
         da.B = B; da.L = L.L; da.C = C; da.H = H; da.r = L.r; da.t = L.t; da.whole = whole ? 1 : 0;
         da.scale = 1.0f / std::sqrt(std::sqrt((float)d));
         da.Wp = Wp; da.ldw = ldp; da.bias = bp;
+        da.Wpk = Wp_pk;                                         // lane-linear copy (made at weight load): the proj B fragments go straight into registers
+        da.form = g_deep_attn_form > 0 ? g_deep_attn_form : 0;
         const bool fuse_env = !deep_opt(MTV_DEEP_OPT_NO_FUSED_ATTN, "MTV_DEEP_NO_ATTN", false);
         const bool deep_qkv_env = deep_opt(MTV_DEEP_OPT_SLICED_QKV, "MTV_DEEP_QKV", false);
         // ---- the whole block in ONE launch (block.hip, k_deep_block): a cluster of workgroups per (clip, head) reads the input's slabs,
@@ -2329,6 +2332,12 @@ int mtv_debug_deep(int mode) {
 int mtv_debug_deep_options(int mask) {
     if (mask < -1 || mask > 127) return fail(MTV_ERR_INVALID, "mask must be -1 (environment / defaults) or a combination of MTV_DEEP_OPT_*");
     g_deep_opts = mask;
+    return MTV_OK;
+}
+
+int mtv_debug_deep_attn_form(int form) {
+    if (form < -1 || form > 2) return fail(MTV_ERR_INVALID, "form must be -1 (the rule / MTV_DEEP_ATTN_HPW), 1 (one head per workgroup) or 2 (head groups)");
+    g_deep_attn_form = form;
     return MTV_OK;
 }
 

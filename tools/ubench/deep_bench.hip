@@ -374,8 +374,10 @@ static void do_chain(int nops, int r, int t, int ks_arg, int nrg_arg) {
 
 
 // ---------------------------------------------------------------------------------------------------------------- k_deep_attn
-static int run_attn(int r, int t, int C, int H, int whole, int res_ks, bool timing) {
-    const int b1 = r * r, b2 = b1 + t * r, L = b2 + t * r, d = C / H, ldw = (C + 63) / 64 * 64, B = 1;
+// form 0: deep_attn_configure's rule without a packed proj_out matrix (the LDS-staged slice); 1: packed matrix + one head per workgroup forced (where that form does not
+// exist: the rule's form, on packed weights); 2: packed matrix, head groups
+static int run_attn(int r, int t, int C, int H, int whole, int res_ks, bool timing, int form = 0, int B = 1) {
+    const int b1 = r * r, b2 = b1 + t * r, L = b2 + t * r, d = C / H, ldw = (C + 63) / 64 * 64;
     std::vector<float> qkv((size_t)B * L * 3 * C), W((size_t)C * ldw), bias(C), xr;
     for (auto& v : qkv) v = frand();
     const float wsc = 1.0f / sqrtf((float)C);
@@ -385,58 +387,73 @@ static int run_attn(int r, int t, int C, int H, int whole, int res_ks, bool timi
     a.qkv = dup(qkv); a.B = B; a.L = L; a.C = C; a.H = H; a.r = r; a.t = t; a.whole = whole;
     a.scale = 1.0f / sqrtf(sqrtf((float)d));
     a.Wp = dup(W); a.ldw = ldw; a.bias = dup(bias);
+    if (form && !(C & 15)) {
+        // ConvArgs::Wpk, restated: lane (j, q) of (column block bn, chunk c) holds the four weights of output channel 16 bn + j for input channels 16 c + 4 q .. + 3
+        std::vector<float> pk((size_t)C * C);
+        const int nch = C / 16;
+        for (int bn = 0; bn < C / 16; ++bn)
+            for (int c = 0; c < nch; ++c)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int e = 0; e < 4; ++e) pk[(((size_t)bn * nch + c) * 64 + lane) * 4 + e] = W[(size_t)(16 * c + 4 * (lane >> 4) + e) * ldw + 16 * bn + (lane & 15)];
+        a.Wpk = dup(pk);
+    }
+    a.form = form;
     a.res = make_src(B, L, C, res_ks, xr);
     if (!deep_attn_configure(a)) { printf("attn L%d d%d: not configurable\n", L, d); return 1; }
-    float* out = dnew<float>((size_t)8 * B * L * C);
-    a.out = out; a.out_slab_stride = (unsigned)((size_t)B * L * C);
+    const size_t LC = (size_t)L * C, slab = (size_t)B * LC;
+    float* out = dnew<float>((size_t)8 * slab);
+    a.out = out; a.out_slab_stride = (unsigned)slab;
 #ifdef MTV_DEEP_STAMP
     a.dbg = dnew<unsigned long long>(64);
 #endif
-    CK(hipMemset(out, 0xFF, (size_t)8 * B * L * C * 4));
+    CK(hipMemset(out, 0xFF, (size_t)8 * slab * 4));
     CK(launch_deep_attn(a, 0));
     CK(hipDeviceSynchronize());
-    std::vector<float> got((size_t)a.nhg * B * L * C);
+    std::vector<float> got((size_t)a.nhg * slab);
     CK(hipMemcpy(got.data(), out, got.size() * 4, hipMemcpyDeviceToHost));
     // CPU reference (double): softmax(q k^T d^-1/2) v per head over the keys the query may see, then proj + bias + residual
-    std::vector<double> att((size_t)L * C), ref((size_t)L * C);
-    for (int h = 0; h < H; ++h)
-        for (int q = 0; q < L; ++q) {
-            const int qp = q >= b2 ? 2 : (q >= b1 ? 1 : 0);
-            std::vector<double> sc(L, -1e300);
-            double mx = -1e300;
-            for (int k = 0; k < L; ++k) {
-                const int kp = k >= b2 ? 2 : (k >= b1 ? 1 : 0);
-                if (!whole && kp != qp) continue;
-                double s = 0;
-                for (int e = 0; e < d; ++e) s += (double)qkv[(size_t)q * 3 * C + h * 3 * d + e] * qkv[(size_t)k * 3 * C + h * 3 * d + d + e];
-                sc[k] = s / sqrt((double)d);
-                mx = std::max(mx, sc[k]);
-            }
-            double den = 0;
-            for (int k = 0; k < L; ++k) if (sc[k] > -1e299) { sc[k] = exp(sc[k] - mx); den += sc[k]; } else sc[k] = 0;
-            for (int e = 0; e < d; ++e) {
-                double o = 0;
-                for (int k = 0; k < L; ++k) o += sc[k] * qkv[(size_t)k * 3 * C + h * 3 * d + 2 * d + e];
-                att[(size_t)q * C + h * d + e] = o / den;
-            }
-        }
-    for (int q = 0; q < L; ++q)
-        for (int n = 0; n < C; ++n) {
-            double o = bias[n] + xr[(size_t)q * C + n];
-            for (int k = 0; k < C; ++k) o += att[(size_t)q * C + k] * W[(size_t)k * ldw + n];
-            ref[(size_t)q * C + n] = o;
-        }
     double worst = 0, sc2 = 0;
     bool nan = false;
-    for (size_t e = 0; e < ref.size(); ++e) {
-        double s2 = 0;
-        for (int k = 0; k < a.nhg; ++k) { const float v = got[(size_t)k * ref.size() + e]; if (v != v) nan = true; s2 += v; }
-        worst = std::max(worst, fabs(s2 - ref[e]));
-        sc2 = std::max(sc2, fabs(ref[e]));
+    for (int b = 0; b < B; ++b) {
+        const float* qb = qkv.data() + (size_t)b * L * 3 * C;
+        std::vector<double> att(LC), ref(LC);
+        for (int h = 0; h < H; ++h)
+            for (int q = 0; q < L; ++q) {
+                const int qp = q >= b2 ? 2 : (q >= b1 ? 1 : 0);
+                std::vector<double> sc(L, -1e300);
+                double mx = -1e300;
+                for (int k = 0; k < L; ++k) {
+                    const int kp = k >= b2 ? 2 : (k >= b1 ? 1 : 0);
+                    if (!whole && kp != qp) continue;
+                    double s = 0;
+                    for (int e = 0; e < d; ++e) s += (double)qb[(size_t)q * 3 * C + h * 3 * d + e] * qb[(size_t)k * 3 * C + h * 3 * d + d + e];
+                    sc[k] = s / sqrt((double)d);
+                    mx = std::max(mx, sc[k]);
+                }
+                double den = 0;
+                for (int k = 0; k < L; ++k) if (sc[k] > -1e299) { sc[k] = exp(sc[k] - mx); den += sc[k]; } else sc[k] = 0;
+                for (int e = 0; e < d; ++e) {
+                    double o = 0;
+                    for (int k = 0; k < L; ++k) o += sc[k] * qb[(size_t)k * 3 * C + h * 3 * d + 2 * d + e];
+                    att[(size_t)q * C + h * d + e] = o / den;
+                }
+            }
+        for (int q = 0; q < L; ++q)
+            for (int n = 0; n < C; ++n) {
+                double o = bias[n] + xr[(size_t)b * LC + (size_t)q * C + n];
+                for (int k = 0; k < C; ++k) o += att[(size_t)q * C + k] * W[(size_t)k * ldw + n];
+                ref[(size_t)q * C + n] = o;
+            }
+        for (size_t e = 0; e < LC; ++e) {
+            double s2 = 0;
+            for (int k = 0; k < a.nhg; ++k) { const float v = got[(size_t)k * slab + (size_t)b * LC + e]; if (v != v) nan = true; s2 += v; }
+            worst = std::max(worst, fabs(s2 - ref[e]));
+            sc2 = std::max(sc2, fabs(ref[e]));
+        }
     }
     const bool ok = !nan && worst <= 1e-4 * std::max(1.0, sc2);
-    printf("attn+proj L%-3d C%-3d d%-2d %s res_ks%d  HPW%d NC%d -> %d slabs, %d WGs  max|err| %.3e (|ref| <= %.2f)%s  %s\n", L, C, d, whole ? "1d" : "2d", res_ks, a.HPW, a.NC,
-           a.nhg, a.ncg * a.B * a.nqg * a.nhg, worst, sc2, nan ? " NaN" : "", ok ? "PASS" : "FAIL");
+    printf("attn+proj L%-3d C%-3d d%-2d %s B%d res_ks%d %s HPW%d NC%d -> %d slabs, %d WGs  max|err| %.3e (|ref| <= %.2f)%s  %s\n", L, C, d, whole ? "1d" : "2d", B, res_ks,
+           form == 0 ? "staged" : (form == 1 ? "packed/heads" : "packed"), a.HPW, a.NC, a.nhg, a.ncg * a.B * a.nqg * a.nhg, worst, sc2, nan ? " NaN" : "", ok ? "PASS" : "FAIL");
     if (timing) {
         hipStream_t s; CK(hipStreamCreate(&s));
         hipGraph_t gr; hipGraphExec_t ge;
@@ -475,6 +492,17 @@ static int do_attn(bool timing) {
     bad += run_attn(8, 4, 256, 8, 1, 1, false);       // d = 32
     bad += run_attn(6, 3, 256, 8, 0, 1, false);       // ragged planes 36 | 18 | 18
     bad += run_attn(3, 1, 128, 2, 0, 1, false);       // 15 tokens, d = 64
+    // packed proj_out matrix (DeepAttnArgs::Wpk), the rule's head groups (form 2) and one head per workgroup with 128-column slices (form 1)
+    for (int form : {2, 1}) {
+        bad += run_attn(8, 4, 512, 8, 1, 1, timing, form);       // the product shape: full key tiles, one proj tile per wave
+        bad += run_attn(8, 4, 512, 8, 1, 8, false, form);
+        bad += run_attn(8, 4, 512, 8, 0, 1, timing, form);
+        bad += run_attn(8, 4, 512, 8, 0, 8, false, form);
+        bad += run_attn(6, 3, 256, 8, 0, 1, false, form);        // ragged planes 36 | 18 | 18: a query tile across a plane border, 5 key tiles (V^T swizzle off)
+        bad += run_attn(3, 1, 128, 2, 0, 1, false, form);        // 15 tokens: fewer keys than a tile, rows past L stay zero
+        bad += run_attn(8, 4, 128, 8, 1, 1, false, form, 2);     // two clips, d = 16: a K slice of ONE chunk
+        bad += run_attn(8, 4, 64, 4, 0, 2, false, form);         // C = 64: no 128-column slice -- form 1 falls back to the rule
+    }
     printf("%s (%d failing)\n", bad ? "ATTN CHECK FAILED" : "ATTN CHECK OK", bad);
     return bad;
 }
