@@ -167,10 +167,6 @@ int mtv_debug_force_lds(int wm, int wn);
  * k_x3_prep + k_conv_x3<mt, nt> (workgroup tile 32 mt x 64 nt, csrc/conv_x3.hip) with `ks` K slices per tile (1, 2, 4, 8;
  * convs with fewer than 6 ks 32-channel chunks keep one slice) instead of the tuned choice; mt = 0: off. */
 int mtv_debug_force_b3(int mt, int nt, int ks);
-/* Testing aid: plans built after this call run every eligible 1x1 convolution (the attention blocks' qkv / proj_out,
- * unet.py:234,253) on the lean kernel k_lin<mt, nt, nwv> (wave tile 16 mt x 16 nt, nwv waves side by side along the
- * output channels, whole K per wave; csrc/lin.hip) instead of the tuned choice; mt = 0 switches it off again. */
-int mtv_debug_force_lin(int mt, int nt, int nwv);
 /* Testing aid: plans built after this call run every eligible 3x3 convolution (ResBlock in_layers / out_layers, unet.py:131-167) on
  * the window-staged kernel k_conv_win<mt, nt> (row tile 16 mt x column tile 16 nt; the transformed input rows of the tile and their
  * halo staged in LDS once, csrc/deep.hip) instead of the tuned choice; mt = 0 switches it off again. */

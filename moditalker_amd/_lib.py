@@ -99,7 +99,6 @@ SYMBOLS = [
     ("mtv_profile_step", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(MtvOpTime), C.c_int, C.POINTER(C.c_int), _P]),
     ("mtv_debug_stamps", C.c_int, [_P, C.c_int, C.c_char_p, _P]),
     ("mtv_debug_force_lds", C.c_int, [C.c_int, C.c_int]),
-    ("mtv_debug_force_lin", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_debug_force_win", C.c_int, [C.c_int, C.c_int]),
     ("mtv_debug_force_win_ks", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_debug_force_pw", C.c_int, [C.c_int, C.c_int]),

@@ -328,7 +328,7 @@ struct AeBuilder {
         auto op = std::make_shared<ConvOp>();
         op->a = a;
         op->t = conv_pick_tile(a.B, rows, N, K / 16, K, false);
-        force_lds_tile(a, &op->t);
+        force_family_tile(a, &op->t);
         op->base_name = "gemm:" + name;
         op->op_index = (int)plan->ops.size();
         plan->convs.push_back(op);
@@ -356,7 +356,7 @@ struct AeBuilder {
     }
     static bool x3_fused_geglu(const ConvOp& op) {
         static const bool off = getenv("MTV_AE_NO_GEGLU_FUSION") != nullptr;
-        return !off && op.t.NW == 48 && !op.a.gather && conv_x3_eligible(op.a) && op.a.x3 != nullptr;
+        return !off && conv_family(op.t) == CONV_X3 && !op.a.gather && conv_x3_eligible(op.a) && op.a.x3 != nullptr;
     }
 
     float* lin_w(const std::string& key, int N, int K, int* ld_out) {        // Linear [N][K] -> [K][ld]

@@ -1261,12 +1261,51 @@ ConvTile conv_pick_tile(int B, int Lout, int N, int nchunks, int Cmain, bool has
 }
 
 size_t conv_smem_bytes(const ConvArgs& a, ConvTile t) {
-    if (t.NW == 80) return conv_win_smem_bytes(a, t);
-    if (t.NW == 96) return conv_pw_smem_bytes(a, t);
-    if (t.NW == 64) return lin_smem_bytes(a);
-    if (t.NW == 48) return conv_x3_smem_bytes(a, t);
-    if (t.NW == 32) return lds_bytes_tiled(t.MT, t.NT, a.ntaps, a.Cmain, a.Cskip, a.gn.sums != nullptr);
-    return lds_bytes(t.MT, t.NT, t.NW, t.KS, a.ntaps, a.Cmain, a.Cskip, a.gn.sums != nullptr);
+    switch (conv_family(t)) {
+        case CONV_WIN: return conv_win_smem_bytes(a, t);
+        case CONV_PW: return conv_pw_smem_bytes(a, t);
+        case CONV_X3: return conv_x3_smem_bytes(a, t);
+        case CONV_LDS: return lds_bytes_tiled(t.MT, t.NT, a.ntaps, a.Cmain, a.Cskip, a.gn.sums != nullptr);
+        default: return lds_bytes(t.MT, t.NT, t.NW, t.KS, a.ntaps, a.Cmain, a.Cskip, a.gn.sums != nullptr);
+    }
+}
+
+// k_conv<MT, NT, NW> and k_conv_lds<WM, WN>: the instantiations (launch_conv's dispatch, conv_init_attrs) and what they can run, within 120 KB of LDS
+static bool conv_plain_tile_exists(const ConvTile& t) {
+    static const int mn[][2] = {{4, 4}, {2, 4}, {1, 4}, {2, 2}, {1, 2}, {1, 1}};
+    bool found = false;
+    for (auto& c : mn) found = found || (t.MT == c[0] && t.NT == c[1]);
+    return found && (t.NW == 1 || t.NW == 2 || t.NW == 4 || t.NW == 8 || t.NW == 16) && !(t.NW == 16 && t.MT * t.NT >= 8) &&
+           t.KS >= 1 && t.KS <= 16 && (t.KS & (t.KS - 1)) == 0 && (t.XM == 0 || t.XM == 1);
+}
+static bool conv_plain_can_run(const ConvArgs& a, const ConvTile& t, size_t slab_cap) {      // (every wave of every K slice gets a chunk)
+    return conv_plain_tile_exists(t) && t.NW * t.KS <= a.ntaps * (a.Cmain / 16) + a.Cskip / 16 && conv_slab_fits(a, t.KS, slab_cap) &&
+           conv_smem_bytes(a, t) <= 120 * 1024;
+}
+static bool conv_lds_tile_exists(const ConvTile& t) { return (t.MT == 2 || t.MT == 4) && (t.NT == 2 || t.NT == 4 || t.NT == 8) && t.KS == 1 && t.XM == 0; }
+static bool conv_lds_can_run(const ConvArgs& a, const ConvTile& t, size_t) {
+    return conv_lds_tile_exists(t) && conv_lds_eligible(a) && conv_smem_bytes(a, t) <= 120 * 1024;
+}
+
+bool conv_tile_exists(const ConvTile& t) {
+    switch (conv_family(t)) {
+        case CONV_PLAIN: return conv_plain_tile_exists(t);
+        case CONV_LDS: return conv_lds_tile_exists(t);
+        case CONV_X3: return conv_x3_tile_exists(t);
+        case CONV_WIN: return conv_win_tile_exists(t);
+        case CONV_PW: return conv_pw_tile_exists(t);
+    }
+    return false;
+}
+bool conv_tile_runs(const ConvArgs& a, const ConvTile& t, size_t slab_cap) {
+    switch (conv_family(t)) {
+        case CONV_PLAIN: return conv_plain_can_run(a, t, slab_cap);
+        case CONV_LDS: return conv_lds_can_run(a, t, slab_cap);
+        case CONV_X3: return conv_x3_can_run(a, t, slab_cap);
+        case CONV_WIN: return conv_win_can_run(a, t, slab_cap);
+        case CONV_PW: return conv_pw_can_run(a, t, slab_cap);
+    }
+    return false;
 }
 
 template <int MT, int NT, int NW>
@@ -1359,48 +1398,27 @@ hipError_t launch_conv(const ConvArgs& a0, ConvTile t, hipStream_t s) {
         a.xmap = 0;            // no padding blocks: every block of the grid takes part in the step hand-over
     }
     hipError_t e = hipErrorInvalidValue;
-    if (t.NW == 80) {            // window-staged 3x3 kernel of the large levels (deep.hip: k_conv_win)
-        if (conv_win_eligible(a, t.MT, t.NT, t.KS)) return launch_conv_win(a, t, s);
-        t = conv_pick_tile(a.B, a.Lout, a.N, a.ntaps * (a.Cmain / 16) + a.Cskip / 16, a.Cmain, a.gn.sums != nullptr);   // (statistics targets are
-        t.KS = 1;                                                                                                       // attached after the op is created)
-        a.KS = 1;
-        a.xmap = t.XM;
-    }
-    if (t.NW == 96) {            // 1x1 kernel of the large levels (deep.hip: k_conv_pw)
-        if (conv_pw_eligible(a, t.MT, t.NT, t.KS)) return launch_conv_pw(a, t, s);
+    // A tile of one of the special kernels that this conv cannot run on after all (statistics targets are attached after a plan's op is
+    // created, so a tile forced at that point can turn out ineligible) gives way to the analytic k_conv tile, unsliced.
+    if (conv_family(t) != CONV_PLAIN && !conv_tile_runs(a, t, CONV_SLAB_ANY)) {
         t = conv_pick_tile(a.B, a.Lout, a.N, a.ntaps * (a.Cmain / 16) + a.Cskip / 16, a.Cmain, a.gn.sums != nullptr);
         t.KS = 1;
         a.KS = 1;
         a.xmap = t.XM;
     }
-    if (t.NW == 48) {            // split-bf16 kernels for large token counts (conv_x3.hip: elementwise pass + gathering GEMM)
-        if (conv_x3_eligible(a) && a.x3) return launch_conv_x3(a, t, s);
-        t = conv_pick_tile(a.B, a.Lout, a.N, a.ntaps * (a.Cmain / 16) + a.Cskip / 16, a.Cmain, a.gn.sums != nullptr);
-        t.KS = 1;
-        a.KS = 1;
-        a.xmap = t.XM;
-    }
-    if (t.NW == 64) {            // lean 1x1 kernel (lin.hip)
-        if (conv_lin_eligible(a)) return launch_lin(a, t, s);
-        t = conv_pick_tile(a.B, a.Lout, a.N, a.ntaps * (a.Cmain / 16) + a.Cskip / 16, a.Cmain, a.gn.sums != nullptr);   // (statistics targets are
-        t.KS = 1;                                                                                                       // attached after the op is created)
-        a.KS = 1;
-        a.xmap = t.XM;
-    }
-    if (t.NW == 32 && !conv_lds_eligible(a)) {      // (statistics targets are attached after a plan's op is created)
-        t = conv_pick_tile(a.B, a.Lout, a.N, a.ntaps * (a.Cmain / 16) + a.Cskip / 16, a.Cmain, a.gn.sums != nullptr);
-        t.KS = 1;
-        a.KS = 1;
-        a.xmap = t.XM;
-    }
-    if (t.NW == 32) {            // LDS-tiled kernel
-        if (t.MT == 4 && t.NT == 4) return launch_conv_lds_t<4, 4>(a, s);
-        if (t.MT == 2 && t.NT == 4) return launch_conv_lds_t<2, 4>(a, s);
-        if (t.MT == 4 && t.NT == 2) return launch_conv_lds_t<4, 2>(a, s);
-        if (t.MT == 2 && t.NT == 2) return launch_conv_lds_t<2, 2>(a, s);
-        if (t.MT == 2 && t.NT == 8) return launch_conv_lds_t<2, 8>(a, s);
-        if (t.MT == 4 && t.NT == 8) return launch_conv_lds_t<4, 8>(a, s);
-        return hipErrorInvalidValue;
+    switch (conv_family(t)) {
+        case CONV_WIN: return launch_conv_win(a, t, s);
+        case CONV_PW: return launch_conv_pw(a, t, s);
+        case CONV_X3: return launch_conv_x3(a, t, s);       // (elementwise pass + gathering GEMM)
+        case CONV_LDS:
+            if (t.MT == 4 && t.NT == 4) return launch_conv_lds_t<4, 4>(a, s);
+            if (t.MT == 2 && t.NT == 4) return launch_conv_lds_t<2, 4>(a, s);
+            if (t.MT == 4 && t.NT == 2) return launch_conv_lds_t<4, 2>(a, s);
+            if (t.MT == 2 && t.NT == 2) return launch_conv_lds_t<2, 2>(a, s);
+            if (t.MT == 2 && t.NT == 8) return launch_conv_lds_t<2, 8>(a, s);
+            if (t.MT == 4 && t.NT == 8) return launch_conv_lds_t<4, 8>(a, s);
+            return hipErrorInvalidValue;
+        default: break;
     }
     if (t.MT == 4 && t.NT == 4) e = launch_conv_nw<4, 4>(a, t.NW, s);
     else if (t.MT == 2 && t.NT == 4) e = launch_conv_nw<2, 4>(a, t.NW, s);

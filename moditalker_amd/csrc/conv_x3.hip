@@ -729,8 +729,9 @@ static size_t x3_lds_t(int ntaps) { return (size_t)x3_tab_bytes(32 * MT, 64 * NT
 
 #define X3_TILES(F) F(4, 2) F(8, 2) F(4, 4) F(2, 2) F(4, 1) F(2, 1) F(8, 1)
 
-bool x3_tile_exists(int MT, int NT) {
-#define X3_E(M, N_) if (MT == M && NT == N_) return true;
+bool conv_x3_tile_exists(const ConvTile& t) {
+    if (!(t.KS == 1 || t.KS == 2 || t.KS == 4 || t.KS == 8) || t.XM != 0) return false;
+#define X3_E(M, N_) if (t.MT == M && t.NT == N_) return true;
     X3_TILES(X3_E)
 #undef X3_E
     return false;
@@ -741,6 +742,14 @@ size_t conv_x3_smem_bytes(const ConvArgs& a, ConvTile t) {
     X3_TILES(X3_S)
 #undef X3_S
     return (size_t)1 << 30;
+}
+
+// (K slices of at least 6 chunks of 32 channels; the activation scratch ConvArgs::x3 is attached with the slab, to every conv that has a W3
+// copy -- finish_split_k -- and is checked at launch)
+bool conv_x3_can_run(const ConvArgs& a, const ConvTile& t, size_t slab_cap) {
+    if (!conv_x3_tile_exists(t) || !conv_x3_eligible(a)) return false;
+    if (t.KS > 1 && 6 * t.KS > a.ntaps * (a.Cmain / 32) + a.Cskip / 32) return false;
+    return conv_slab_fits(a, t.KS, slab_cap) && conv_x3_smem_bytes(a, t) <= CONV_X3_MAX_LDS;
 }
 
 static hipError_t launch_x3_prep(const ConvArgs& a, hipStream_t s, const float* geglu_h = nullptr) {

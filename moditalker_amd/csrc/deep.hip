@@ -1637,7 +1637,7 @@ __global__ __launch_bounds__(DEEP_NTH) void k_conv_win(const ConvArgs a) {
 // but re-derived the GroupNorm coefficients and re-transformed the rows per wave.  Here the 16 MT rows of a workgroup are normalised ONCE
 // into LDS (k_conv_win's prologue: statistics -> (mean, rstd) through one barrier, per-thread coefficients of one channel quad), the 8
 // waves sit side by side along N (16 NTW columns each, whole K, no reduction), weights come in the checkpoint's own [N][K] layout
-// (ConvArgs::Wnk: lane (j, q) loads W[n][c0 + 4q .. + 3], one 16-byte request per 16-channel chunk and column block), requested
+// (since round 6 repacked lane-linear, ConvArgs::Wpk: lane (j, q) loads W[n][c0 + 4q .. + 3], one 16-byte request per 16-channel chunk and column block), requested
 // between the rows of the transform, and the accumulators go through LDS once so that stores, residual reads and statistics are
 // 16-byte wide.  Workgroup = (clip, row tile, group of 128 NTW columns), 512 threads.
 // (round 6: NWA = the waves that multiply -- 8, 6, 4 or 2 -- so that the column tile is 16 NTW NWA wide and the grid can be made to FILL the chip:
@@ -2274,9 +2274,12 @@ int conv_win_selftest(int r, int t, bool up, int Lout, int Lsrc) {
     return 0;
 }
 
+bool conv_win_tile_exists(const ConvTile& t) {
+    return (t.MT == 1 || t.MT == 2) && (t.NT == 2 || t.NT == 4) &&       // (2 x 4: round 6, with a 2 x 2-chunk weight ring)
+           (t.KS == 1 || t.KS == 2 || t.KS == 4) && (t.XM == 0 || t.XM == 1);
+}
 bool conv_win_eligible(const ConvArgs& a, int MT, int NT, int KS) {
-    if (!((MT == 1 && (NT == 2 || NT == 4)) || (MT == 2 && (NT == 2 || NT == 4)))) return false;       // (2 x 4: round 6, with a 2 x 2-chunk weight ring)
-    if (KS != 1 && KS != 2 && KS != 4) return false;
+    if (!conv_win_tile_exists(ConvTile{MT, NT, CONV_WIN, KS, 0})) return false;
     // K slices: whole 16-channel chunks of the tapped and of the skip channels per slice; slab + counters of the plan (attached to every
     // conv by finish_split_k: checked at launch, not here -- tiles are chosen before that)
     if (KS > 1 && ((a.Cskip / 16) % KS || (a.Cmain / 16) % KS || (a.N & 3))) return false;
@@ -2288,6 +2291,9 @@ bool conv_win_eligible(const ConvArgs& a, int MT, int NT, int KS) {
         if (a.stat[t].coff & 3) return false;
     if ((long)(9 * a.Cmain + a.Cskip) * a.ldw * 4 >= 0x7F000000L) return false;
     return conv_win_layout(a, MT, NT, KS, nullptr) <= 160 * 1024;
+}
+bool conv_win_can_run(const ConvArgs& a, const ConvTile& t, size_t slab_cap) {
+    return conv_win_tile_exists(t) && conv_win_eligible(a, t.MT, t.NT, t.KS) && conv_slab_fits(a, t.KS, slab_cap);
 }
 size_t conv_win_smem_bytes(const ConvArgs& a, ConvTile t) { return conv_win_layout(a, t.MT, t.NT, t.KS < 1 ? 1 : t.KS, nullptr); }
 
@@ -2354,10 +2360,13 @@ static size_t conv_pw_layout(const ConvArgs& a, int MT, int NTW, int NWA) {
     const size_t image = (size_t)ROWS * (COLS + 4) + DEEP_FIN_FLOATS;
     return (stage > image ? stage : image) * 4 + 64;
 }
+bool conv_pw_tile_exists(const ConvTile& t) {
+    return (t.MT == 1 || t.MT == 2) && (t.NT == 1 || t.NT == 2) &&             // (NTW = 3 measured slower than 1 and 2 on every shape: not built)
+           (t.KS == 1 || (t.NT == 1 && (t.KS == 6 || t.KS == 4 || t.KS == 2))) && (t.XM == 0 || t.XM == 1);
+}
 bool conv_pw_eligible(const ConvArgs& a, int MT, int NTW, int wcode) {
     const int NWA = conv_pw_waves(wcode);
-    if (!((MT == 1 || MT == 2) && (NTW == 1 || NTW == 2))) return false;       // (NTW = 3 measured slower than 1 and 2 on every shape: not built)
-    if (!(NWA == 8 || (NTW == 1 && (NWA == 6 || NWA == 4 || NWA == 2)))) return false;
+    if (!conv_pw_tile_exists(ConvTile{MT, NTW, CONV_PW, NWA == 8 ? 1 : NWA, 0})) return false;
     if (!a.Wpk || (a.N & 15) || a.ntaps != 1 || a.nmain != 1 || a.nskip != 0 || a.Cskip != 0 || a.gather || a.gather_skip || a.geo_main || a.geo_skip) return false;
     if (a.out_cm || a.ddim || a.bias_b || a.bias2) return false;
     if ((a.Cmain & 15) || a.Cmain < 64 || a.Cmain > 512 || (512 % (a.Cmain >> 2)) || a.N % (16 * NTW) || a.Lsrc != a.Lout || (a.res && a.Lskip != a.Lout)) return false;
@@ -2366,6 +2375,9 @@ bool conv_pw_eligible(const ConvArgs& a, int MT, int NTW, int wcode) {
         if (a.stat[t].coff & 3) return false;
     if ((long)a.N * a.Cmain * 4 >= 0x7F000000L) return false;
     return conv_pw_layout(a, MT, NTW, NWA) <= 160 * 1024;
+}
+bool conv_pw_can_run(const ConvArgs& a, const ConvTile& t, size_t) {     // (no K slices: no slab)
+    return conv_pw_tile_exists(t) && conv_pw_eligible(a, t.MT, t.NT, t.KS);
 }
 size_t conv_pw_smem_bytes(const ConvArgs& a, ConvTile t) { return conv_pw_layout(a, t.MT, t.NT, conv_pw_waves(t.KS)); }
 

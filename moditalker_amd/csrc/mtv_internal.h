@@ -76,7 +76,6 @@ struct ConvArgs {
     int Lout, Lsrc, Lskip;   // tokens per batch element: output, tapped source, skip/residual source
     int B;
     const float* W;          // rows [ntaps*Cmain + Cskip][ldw], columns = output channels
-    const float* Wnk;        // 1x1 convs on identity rows only: the same weight as stored in the checkpoint, [N][Cmain] (k_lin, lin.hip)
     const float* Wpk;        // 1x1 convs on identity rows only (N, Cmain multiples of 16): k_conv_pw's operand [N / 16][Cmain / 16][64 lanes][4] -- lane (j, q) of (column
                              // block bn, chunk c) holds W[16 bn + j][16 c + 4 q .. + 3], so a wave's B fragment of a chunk is ONE contiguous KB (k_repack_pw, kernels.hip)
     const void* W3;          // the same matrix as three bf16 planes [3][K/8][ldw][8] with W = W0 + W1 + W2 (k_conv_x3, conv_x3.hip) or nullptr
@@ -464,31 +463,47 @@ __device__ __forceinline__ float ddim_update_elem(const DdimStep& st, float x, f
 
 // ---- launchers (kernels.hip) ----
 struct ConvTile { int MT, NT, NW, KS, XM; };   // XM: workgroup->tile mapping (0 rows fastest, 1 weight slice per XCD)
-                                               // NW == 32: the LDS-tiled kernel k_conv_lds<WM = MT, WN = NT> (KS = 1, XM = 0)
-                                               // NW == 64: the lean 1x1 kernel k_lin<MT, NT, NWV = KS> (lin.hip; XM = 0)
-                                               // NW == 48: the split-bf16 kernels k_x3_prep + k_conv_x3<MT, NT> (conv_x3.hip; KS = 1, XM = 0)
+// The kernel family of a tile is ConvTile::NW: <= 16 is k_conv<MT, NT, NW> itself (NW waves per workgroup), the other kernels have a code
+// each -- the numbers the tile table (tune_gfx950.txt) and the launch tags "t MT,NT,NW,KS" carry.
+enum ConvFamily : int {
+    CONV_PLAIN = 0,          // k_conv<MT, NT, NW> (conv.hip), KS K slices
+    CONV_LDS = 32,           // the LDS-tiled kernel k_conv_lds<WM = MT, WN = NT> (conv.hip; KS = 1, XM = 0)
+    CONV_X3 = 48,            // the split-bf16 kernels k_x3_prep + k_conv_x3<MT, NT> (conv_x3.hip; KS K slices, XM = 0)
+    CONV_WIN = 80,           // k_conv_win<MT, NT> (deep.hip): 3x3 convs of the large levels, the transformed input window staged in LDS; KS K slices
+    CONV_PW = 96,            // k_conv_pw<MT, NTW> (deep.hip): 1x1 conv on identity rows, rows normalised once into LDS; KS = multiplying waves (1 = all 8, else 6 / 4 / 2)
+};
+inline ConvFamily conv_family(const ConvTile& t) { return t.NW <= 16 ? CONV_PLAIN : (ConvFamily)t.NW; }     // (a code no family has: nobody can launch that tile)
+inline bool conv_ks_is_slices(ConvFamily f) { return f != CONV_PW; }     // ConvTile::KS counts K slices that meet in the plan's slab (k_conv_pw: a wave count)
+// Every family states its rule twice, next to its launcher: conv_*_tile_exists(t) -- the tile is instantiated (shape-independent: what a forced
+// tile is validated with) -- and conv_*_can_run(a, t, slab_cap) -- this conv can run on this tile, the family's LDS bound included; slab_cap =
+// floats of the plan's split-K slab, CONV_SLAB_ANY where it is not known (tiles forced before the slab is sized; launch_conv).
+// conv_tile_exists / conv_tile_runs (conv.hip) dispatch on the family.
+constexpr size_t CONV_SLAB_ANY = ~(size_t)0;
+inline bool conv_slab_fits(const ConvArgs& a, int KS, size_t slab_cap) { return KS <= 1 || (!(a.N & 3) && (size_t)KS * a.B * a.Lout * a.N <= slab_cap); }
 constexpr size_t CONV_X3_MAX_LDS = 160 * 1024;          // k_conv_x3 has no static LDS: the whole 160 KB
 bool conv_x3_eligible(const ConvArgs& a);
-bool x3_tile_exists(int MT, int NT);
+bool conv_x3_tile_exists(const ConvTile& t);
+bool conv_x3_can_run(const ConvArgs& a, const ConvTile& t, size_t slab_cap);
 size_t conv_x3_scratch_bytes(int B, int Lsrc, int Cmain, int Lskip, int Cskip);
 size_t conv_x3_smem_bytes(const ConvArgs& a, ConvTile t);
 hipError_t conv_x3_init_attrs();
 hipError_t launch_conv_x3(const ConvArgs& a, ConvTile t, hipStream_t s);
 hipError_t launch_conv_x3_geglu(const ConvArgs& a, ConvTile t, const float* h, hipStream_t s);
 hipError_t launch_split_w3(const float* W, void* W3, size_t plane_bytes, int row0, int rows, int ldw, hipStream_t s);
-// k_conv_win (deep.hip): 3x3 convs of the large levels with the transformed input window staged in LDS -- ConvTile NW == 80
 bool conv_win_eligible(const ConvArgs& a, int MT, int NT, int KS = 1);     // KS = ConvTile::KS of the tile: K slices (1 | 2 | 4)
+bool conv_win_tile_exists(const ConvTile& t);
+bool conv_win_can_run(const ConvArgs& a, const ConvTile& t, size_t slab_cap);
 int conv_win_selftest(int r, int t, bool up, int Lout, int Lsrc);      // host-only check of the window arithmetic (0 = ok)
 size_t conv_win_smem_bytes(const ConvArgs& a, ConvTile t);
 hipError_t launch_conv_win(const ConvArgs& a, ConvTile t, hipStream_t s);
-// k_conv_pw<MT, NTW> (deep.hip): 1x1 conv on identity rows, rows normalised once into LDS, waves side by side along N (ConvTile NW = 96)
 bool conv_pw_eligible(const ConvArgs& a, int MT, int NTW, int wcode = 1);     // wcode = ConvTile::KS of the tile: 1 = all 8 waves multiply, 6 / 4 / 2 = that many (column tile 16 NTW x waves)
+bool conv_pw_tile_exists(const ConvTile& t);
+bool conv_pw_can_run(const ConvArgs& a, const ConvTile& t, size_t slab_cap);
 size_t conv_pw_smem_bytes(const ConvArgs& a, ConvTile t);
 hipError_t launch_conv_pw(const ConvArgs& a, ConvTile t, hipStream_t s);
-bool conv_lin_eligible(const ConvArgs& a);
-size_t lin_smem_bytes(const ConvArgs& a);
-hipError_t launch_lin(const ConvArgs& a, ConvTile t, hipStream_t s);
 bool conv_lds_eligible(const ConvArgs& a);
+bool conv_tile_exists(const ConvTile& t);
+bool conv_tile_runs(const ConvArgs& a, const ConvTile& t, size_t slab_cap);
 ConvTile conv_pick_tile(int B, int Lout, int N, int nchunks, int Cmain, bool has_gn);
 size_t conv_smem_bytes(const ConvArgs& a, ConvTile t);
 hipError_t launch_conv(const ConvArgs& a, ConvTile t, hipStream_t s);

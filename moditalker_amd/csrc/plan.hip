@@ -267,7 +267,7 @@ struct Builder {
 
     static std::string conv_tag(const ConvArgs& a, const ConvTile& t) {
         char tag[80];
-        snprintf(tag, sizeof tag, "[%dx%d k%d t%d,%d,%d,%d%s]", a.Lout, a.N, a.ntaps * a.Cmain + a.Cskip, t.MT, t.NT, t.NW, t.KS, t.XM ? "x" : "");   // (NW 32: k_conv_lds, NW 64: k_lin)
+        snprintf(tag, sizeof tag, "[%dx%d k%d t%d,%d,%d,%d%s]", a.Lout, a.N, a.ntaps * a.Cmain + a.Cskip, t.MT, t.NT, t.NW, t.KS, t.XM ? "x" : "");   // (NW: the ConvFamily code, mtv_internal.h)
         return tag;
     }
 
@@ -303,7 +303,7 @@ struct Builder {
         auto op = std::make_shared<ConvOp>();
         op->a = a0;
         op->t = conv_pick_tile(B, a0.Lout, a0.N, nchunks, a0.Cmain, a0.gn.sums != nullptr);
-        force_lds_tile(a0, &op->t);
+        force_family_tile(a0, &op->t);
         op->base_name = std::string(a0.ntaps == 9 ? "conv3:" : "conv1:") + name;
         op->op_index = (int)plan->ops.size();
         producer[a0.out] = op;
@@ -768,7 +768,7 @@ struct Builder {
         const int ldq = pad64(3 * C);
         float* Wq = c->buf("w." + P + "qkv.weight", (size_t)C * ldq);
         wconv(P + "qkv.weight", 3 * C, C, 1, 1, true, Wq, ldq);
-        float* Wq_nk = c->buf("wnk." + P + "qkv.weight", (size_t)3 * C * C);      // the same weights as stored, [3C][C]: k_lin's operand
+        float* Wq_nk = c->buf("wnk." + P + "qkv.weight", (size_t)3 * C * C);      // the same weights as stored, [3C][C]: k_deep_block's operand
         c->slots[c->slot_index[P + "qkv.weight"]].dst2 = Wq_nk;
         float* Wq_pk = (C & 15) ? nullptr : c->buf("wpk." + P + "qkv.weight", (size_t)3 * C * C);      // ... and lane-linear: k_conv_pw's operand
         c->slots[c->slot_index[P + "qkv.weight"]].dst3 = Wq_pk;
@@ -938,7 +938,7 @@ struct Builder {
         add_stats({x}, lvl, site);
         float* qkv = c->act(nm + ".qkv", lvl, 3 * C);
         ConvArgs a{};
-        a.ntaps = 1; a.Lout = L.L; a.Lsrc = L.L; a.N = 3 * C; a.W = Wq; a.Wnk = Wq_nk; a.Wpk = Wq_pk; a.ldw = ldq; a.bias = bq; a.out = qkv;
+        a.ntaps = 1; a.Lout = L.L; a.Lsrc = L.L; a.N = 3 * C; a.W = Wq; a.Wpk = Wq_pk; a.ldw = ldq; a.bias = bq; a.out = qkv;
         a.nmain = 1; a.src[0] = x.p; a.C[0] = C; a.Cmain = C; a.seg_src = L.seg();
         a.gn = GnIn{site, gw, gb, nullptr, 0, C / 32, whole ? 1 : 0, 0, (unsigned)c->stats_copy_doubles};
         add_conv(a, nm + ".qkv", lvl);
@@ -950,7 +950,7 @@ struct Builder {
         Tens out;
         out.lvl = lvl; out.C = C; out.p = c->act(nm + ".out", lvl, C);
         ConvArgs p{};
-        p.ntaps = 1; p.Lout = L.L; p.Lsrc = L.L; p.Lskip = L.L; p.N = C; p.W = Wp; p.Wnk = Wp_nk; p.Wpk = Wp_pk; p.ldw = ldp; p.bias = bp; p.out = out.p;
+        p.ntaps = 1; p.Lout = L.L; p.Lsrc = L.L; p.Lskip = L.L; p.N = C; p.W = Wp; p.Wpk = Wp_pk; p.ldw = ldp; p.bias = bp; p.out = out.p;
         p.nmain = 1; p.src[0] = att; p.C[0] = C; p.Cmain = C; p.seg_src = L.seg();
         p.res = x.p;
         add_conv(p, nm + ".proj", lvl);
@@ -1092,83 +1092,54 @@ struct Builder {
 
 // Empirical tile selection: every distinct conv shape of the plan is timed once over the valid
 // (MT, NT, NW, KS) candidates with its real arguments (MTV_AUTOTUNE=0 keeps the analytic pick).
-// testing aid: MTV_FORCE_LDS="WM,WN" (or mtv_debug_force_lds) runs every eligible conv of plans built afterwards on the
-// LDS-tiled kernel k_conv_lds<WM, WN>; a conv that turns out not to be eligible at launch falls back (launch_conv)
-static int g_force_wm = -1, g_force_wn = 0;
-static int g_force_b3[3] = {-1, 0, 1};       // MTV_FORCE_B3="MT,NT[,KS]" (or mtv_debug_force_b3): every eligible conv on the split-bf16 kernel k_conv_x3<MT, NT>
-static int g_force_pw[3] = {-1, 0, 1};         // MTV_FORCE_PW="MT,NTW" (or mtv_debug_force_pw): every eligible 1x1 conv on k_conv_pw<MT, NTW>
-static int g_force_win[3] = {-1, 0, 1};     // MTV_FORCE_WIN="MT,NT[,KS]" (or mtv_debug_force_win / _ks): every eligible 3x3 conv on k_conv_win<MT, NT>
-static int g_force_lin[3] = {-1, 0, 0};     // MTV_FORCE_LIN="MT,NT,NWV" (or mtv_debug_force_lin): every eligible 1x1 conv on k_lin<MT, NT, NWV>
-static void parse_force_b3() {
-    if (g_force_b3[0] != -1) return;
-    g_force_b3[0] = 0;
-    if (const char* e = getenv("MTV_FORCE_B3")) {
+// testing aids: a forced tile of one kernel family runs every conv of plans built afterwards that the family can run on that tile; a conv that
+// turns out not to be eligible at launch falls back (launch_conv).  Set from the environment (read once, on first use) or by mtv_debug_force_*:
+// both go through force_set, so a value one accepts the other accepts.
+struct ForcedTile {
+    const char* env;        // "MT,NT[,KS]"
+    ConvFamily fam;
+    int v[3];               // MT (-1: environment not read yet, 0: off), NT, KS
+};
+static ForcedTile g_force_win{"MTV_FORCE_WIN", CONV_WIN, {-1, 0, 1}};     // every eligible 3x3 conv on k_conv_win<MT, NT>, KS K slices where the conv can take them
+static ForcedTile g_force_pw{"MTV_FORCE_PW", CONV_PW, {-1, 0, 1}};        // every eligible 1x1 conv on k_conv_pw<MT, NTW>; third number: multiplying waves (1 or 8 = all)
+static ForcedTile g_force_b3{"MTV_FORCE_B3", CONV_X3, {-1, 0, 1}};        // every eligible conv on the split-bf16 kernel k_conv_x3<MT, NT>
+static ForcedTile g_force_lds{"MTV_FORCE_LDS", CONV_LDS, {-1, 0, 1}};     // every eligible conv on the LDS-tiled kernel k_conv_lds<WM, WN>
+static bool force_set(ForcedTile& f, int mt, int nt, int ks) {
+    if (mt == 0) { f.v[0] = 0; return true; }
+    if (f.fam == CONV_PW && ks == 8) ks = 1;
+    if (!conv_tile_exists(ConvTile{mt, nt, f.fam, ks, 0})) return false;
+    f.v[0] = mt; f.v[1] = nt; f.v[2] = ks;
+    return true;
+}
+static const ForcedTile& force_env(ForcedTile& f) {
+    if (f.v[0] == -1) {
+        f.v[0] = 0;
         int x = 0, y = 0, z = 1;
-        const int n = sscanf(e, "%d,%d,%d", &x, &y, &z);
-        if (n >= 2 && x3_tile_exists(x, y) && (z == 1 || z == 2 || z == 4 || z == 8)) { g_force_b3[0] = x; g_force_b3[1] = y; g_force_b3[2] = z; }
+        const char* e = getenv(f.env);
+        if (e && sscanf(e, "%d,%d,%d", &x, &y, &z) >= 2) force_set(f, x, y, z);
     }
+    return f;
 }
 // Convs of at least X3_MIN_ROWS tokens (all clips together) get a split-bf16 weight copy + activation scratch and are offered to
 // the tuner on k_conv_x3; below that the elementwise pass and the few 128-row tiles cannot pay (profiles/r03_conv_x3_bench.txt).
 // A forced tile (tests) lifts the bound.
-bool x3_wanted(long rows) {
-    parse_force_b3();
-    return rows >= X3_MIN_ROWS || g_force_b3[0] > 0;
-}
+bool x3_wanted(long rows) { return rows >= X3_MIN_ROWS || force_env(g_force_b3).v[0] > 0; }
+// (... but never the one-clip step at R = 32, the metric's workload: it stays on the exact-f32 instruction throughout)
+static bool x3_tuner_offers(const ConvArgs& a) { return !(a.B == 1 && a.Lout <= 2048); }
 static bool deep_forced_off() {
-    parse_force_b3();
-    return g_force_wm > 0 || g_force_lin[0] > 0 || g_force_b3[0] > 0 || getenv("MTV_FORCE_TILE") || getenv("MTV_FORCE_LDS") || getenv("MTV_FORCE_LIN");     // (not MTV_FORCE_WIN:
-                                                                                                                                                           //  k_conv_win serves the large levels)
+    return g_force_lds.v[0] > 0 || force_env(g_force_b3).v[0] > 0 || getenv("MTV_FORCE_TILE") || getenv("MTV_FORCE_LDS");     // (not MTV_FORCE_WIN: k_conv_win serves
+                                                                                                                             //  the large levels)
 }
-void force_lds_tile(const ConvArgs& a, ConvTile* t) {
-    if (g_force_lin[0] == -1) {
-        g_force_lin[0] = 0;
-        if (const char* e = getenv("MTV_FORCE_LIN")) {
-            int x = 0, y = 0, z = 0;
-            if (sscanf(e, "%d,%d,%d", &x, &y, &z) == 3 && (x == 1 || x == 2) && (y == 1 || y == 2 || y == 4) && (z == 1 || z == 2 || z == 4)) { g_force_lin[0] = x; g_force_lin[1] = y; g_force_lin[2] = z; }
-        }
+void force_family_tile(const ConvArgs& a, ConvTile* t) {
+    static const int win_xm = getenv("MTV_FORCE_WIN_XM") ? atoi(getenv("MTV_FORCE_WIN_XM")) != 0 : 0;      // (k_conv_win with the XCD-aware block order)
+    for (ForcedTile* f : {&g_force_win, &g_force_pw, &g_force_b3, &g_force_lds}) {      // (in this order: the first family that can run the conv takes it)
+        if (force_env(*f).v[0] <= 0) continue;
+        ConvTile ft{f->v[0], f->v[1], f->fam, f->v[2], f->fam == CONV_WIN ? win_xm : 0};
+        // (K slices where the conv can take them -- k_conv_win: no fused skip conv, whole chunks per slice; k_conv_x3: at least 6 chunks each --
+        // else the unsliced tile; the slab is sized after the tiles are chosen, finish_split_k)
+        if (conv_ks_is_slices(f->fam) && !conv_tile_runs(a, ft, CONV_SLAB_ANY)) ft.KS = 1;
+        if (conv_tile_runs(a, ft, CONV_SLAB_ANY)) { *t = ft; return; }
     }
-    if (g_force_lin[0] > 0 && conv_lin_eligible(a)) { *t = ConvTile{g_force_lin[0], g_force_lin[1], 64, g_force_lin[2], 0}; return; }
-    if (g_force_win[0] == -1) {
-        g_force_win[0] = 0;
-        if (const char* e = getenv("MTV_FORCE_WIN")) {
-            int x = 0, y = 0, z = 1;
-            if (sscanf(e, "%d,%d,%d", &x, &y, &z) >= 2 && (x == 1 || x == 2) && (y == 2 || y == 4) && (z == 1 || z == 2 || z == 4)) { g_force_win[0] = x; g_force_win[1] = y; g_force_win[2] = z; }
-        }
-    }
-    if (g_force_win[0] > 0) {
-        static const int xm = getenv("MTV_FORCE_WIN_XM") ? atoi(getenv("MTV_FORCE_WIN_XM")) != 0 : 0;      // (with the XCD-aware block order)
-        // (K slices where the conv can take them -- no fused skip conv, whole chunks per slice -- else the unsliced tile)
-        const int ks = conv_win_eligible(a, g_force_win[0], g_force_win[1], g_force_win[2]) ? g_force_win[2] : 1;
-        if (conv_win_eligible(a, g_force_win[0], g_force_win[1], ks)) {
-            *t = ConvTile{g_force_win[0], g_force_win[1], 80, ks, xm};
-            return;
-        }
-    }
-    if (g_force_pw[0] == -1) {
-        g_force_pw[0] = 0;
-        if (const char* e = getenv("MTV_FORCE_PW")) {
-            int x = 0, y = 0;
-            int z = 1;
-            const int nf = sscanf(e, "%d,%d,%d", &x, &y, &z);
-            if (nf >= 2 && (x == 1 || x == 2) && (y == 1 || y == 2) && (z == 1 || z == 2 || z == 4 || z == 6)) { g_force_pw[0] = x; g_force_pw[1] = y; g_force_pw[2] = z; }
-        }
-    }
-    if (g_force_pw[0] > 0 && conv_pw_eligible(a, g_force_pw[0], g_force_pw[1], g_force_pw[2])) { *t = ConvTile{g_force_pw[0], g_force_pw[1], 96, g_force_pw[2], 0}; return; }
-    parse_force_b3();
-    if (g_force_b3[0] > 0 && conv_x3_eligible(a) && conv_x3_smem_bytes(a, ConvTile{g_force_b3[0], g_force_b3[1], 48, 1, 0}) <= CONV_X3_MAX_LDS) {
-        const int nch32 = a.ntaps * (a.Cmain / 32) + a.Cskip / 32;
-        *t = ConvTile{g_force_b3[0], g_force_b3[1], 48, nch32 >= 6 * g_force_b3[2] ? g_force_b3[2] : 1, 0};     // (K slices of at least 6 chunks)
-        return;
-    }
-    if (g_force_wm == -1) {
-        g_force_wm = 0;
-        if (const char* e = getenv("MTV_FORCE_LDS")) {
-            int x = 0, y = 0;
-            if (sscanf(e, "%d,%d", &x, &y) == 2 && (x == 2 || x == 4) && (y == 2 || y == 4 || y == 8)) { g_force_wm = x; g_force_wn = y; }
-        }
-    }
-    if (g_force_wm > 0 && conv_lds_eligible(a)) *t = ConvTile{g_force_wm, g_force_wn, 32, 1, 0};
 }
 
 // One slab shared by every cross-workgroup split-K conv of a plan (they run back to back), sized so the auto-tuner may
@@ -1184,7 +1155,7 @@ int finish_split_k(mtv_ctx* c, Plan* plan) {
         const size_t one = (size_t)B * op->a.Lout * op->a.N;
         size_t ks = 16;
         while (ks > 1 && ks * one * 4 > ((size_t)64 << 20)) ks /= 2;
-        if (op->t.NW != 64 && op->t.NW != 96 && (size_t)op->t.KS > ks) ks = op->t.KS;      // (k_lin's / k_conv_pw's KS is a wave count)
+        if (conv_ks_is_slices(conv_family(op->t)) && (size_t)op->t.KS > ks) ks = op->t.KS;
         if (ks < 2) continue;                       // never split: needs no slab (the autoencoder's 16384-token GEMMs)
         need = ks * one > need ? ks * one : need;
     }
@@ -1256,12 +1227,26 @@ static void tune_cache_append(const char* key, const ConvTile& t) {
     }
 }
 
+// A 1x1 conv on identity rows that has a packed weight copy (ConvArgs::Wpk): the qkv / proj_out convs of the attention blocks, as far as
+// their epilogue is the plain one.  The class of the tile table's "<key> l" entries (almost all of them k_conv_pw tiles).
+static bool conv_packed_1x1(const ConvArgs& a) {
+    if (!a.Wpk || a.ntaps != 1 || a.nmain != 1 || a.nskip != 0 || a.Cskip != 0 || a.gather || a.gather_skip || a.geo_main || a.geo_skip) return false;
+    if (a.out_cm || a.ddim || a.bias_b || a.bias2 || a.gn.film) return false;
+    if ((a.Cmain & 15) || (a.N & 3) || a.Lsrc != a.Lout || (a.res && a.Lskip != a.Lout)) return false;
+    for (int t = 0; t < a.nstat; ++t) {
+        const int gs = a.stat[t].gs;
+        if ((gs & 3) || (a.stat[t].coff % gs)) return false;      // (statistics groups of whole 4-column quads, starting on a group boundary ...
+        if ((gs & (gs - 1)) == 0 && gs > 64) return false;        //  ... and no power-of-two group wider than 64 columns)
+    }
+    return true;
+}
+
 int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
     if (p->tuned) return MTV_OK;
     p->tuned = true;
     tune_cache_load(c);
     const char* env = getenv("MTV_AUTOTUNE");
-    if ((env && atoi(env) == 0) || getenv("MTV_FORCE_TILE") || g_force_wm > 0 || g_force_lin[0] > 0 || g_force_b3[0] > 0 || g_force_win[0] > 0 || g_force_pw[0] > 0) return MTV_OK;
+    if ((env && atoi(env) == 0) || getenv("MTV_FORCE_TILE") || g_force_lds.v[0] > 0 || g_force_b3.v[0] > 0 || g_force_win.v[0] > 0 || g_force_pw.v[0] > 0) return MTV_OK;
     static const int cand[][2] = {{4, 4}, {2, 4}, {1, 4}, {2, 2}, {1, 2}, {1, 1}};
     struct Events {             // destroyed on every exit path (HIPCHK returns early)
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1287,44 +1272,21 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
         char key[176];
         snprintf(key, sizeof key, "B%d L%d/%d/%d N%d t%d C%d+%d gn%d f%d r%d s%d cm%d", a.B, a.Lout, a.Lsrc, a.Lskip, a.N, a.ntaps, a.Cmain, a.Cskip,
                  a.gn.sums ? 1 : 0, a.gn.film ? 1 : 0, a.res ? 1 : 0, a.nstat, a.out_cm);
-        // Two 1x1 convs can share a shape key and differ in whether the lean kernel (k_lin: identity rows, [N][K] weight copy) can run
-        // them.  Whatever order they are met in, each has its own entry: "<key> l" for the one k_lin can run (falling back to a plain
-        // "<key>" of an older table), the plain key for the other -- unless that holds a k_lin tile, then "<key> x".
-        const bool lin_ok_conv = conv_lin_eligible(a);
-        bool lin_fallback = false;      // the entry found is the plain "<key>" of an older table, possibly the non-k_lin twin's
-        auto it = c->tune_cache.end();
-        if (lin_ok_conv) {
-            char kl[192];
-            snprintf(kl, sizeof kl, "%s l", key);
-            it = c->tune_cache.find(kl);
-            if (it == c->tune_cache.end()) { it = c->tune_cache.find(key); lin_fallback = it != c->tune_cache.end(); }
-            if (it == c->tune_cache.end()) snprintf(key, sizeof key, "%s", kl);     // a new measurement goes under the "l" key
-        } else {
-            it = c->tune_cache.find(key);
-            if (it != c->tune_cache.end() && it->second.NW == 64) {
-                strncat(key, " x", sizeof key - strlen(key) - 1);
-                it = c->tune_cache.find(key);
-            }
+        // Two 1x1 convs can share a shape key and differ in being a packed 1x1 conv on identity rows (conv_packed_1x1).  Whatever order they
+        // are met in, each has its own entry: "<key> l" for the packed one -- which borrows the plain "<key>" of a table written before the
+        // classes were told apart -- and the plain key for the other.
+        auto it = c->tune_cache.find(key);
+        bool borrowed = false;          // the entry found may be the other conv's: it stays when this conv cannot use it
+        if (conv_packed_1x1(a)) {
+            strncat(key, " l", sizeof key - strlen(key) - 1);       // (whatever is measured for this conv goes under its own key)
+            const auto own = c->tune_cache.find(key);
+            borrowed = own == c->tune_cache.end() && it != c->tune_cache.end();
+            if (!borrowed) it = own;
         }
-        if (it != c->tune_cache.end()) {             // an entry read from MTV_TUNE_CACHE is only trusted if it is launchable
-            const ConvTile& t = it->second;
-            const int nchunks = a.ntaps * (a.Cmain / 16) + a.Cskip / 16;
-            const bool tiled_ok = t.NW == 32 && (t.MT == 2 || t.MT == 4) && (t.NT == 2 || t.NT == 4 || t.NT == 8) && t.KS == 1 && t.XM == 0 && conv_lds_eligible(a);
-            const bool lin_ok = t.NW == 64 && (t.MT == 1 || t.MT == 2) && (t.NT == 1 || t.NT == 2 || t.NT == 4) && (t.KS == 1 || t.KS == 2 || t.KS == 4) && t.XM == 0 && conv_lin_eligible(a);
-            const bool b3_ok = t.NW == 48 && !(a.B == 1 && a.Lout <= 2048) && x3_tile_exists(t.MT, t.NT) && (t.KS == 1 || t.KS == 2 || t.KS == 4 || t.KS == 8) && t.XM == 0 && t.KS * 6 <= a.ntaps * (a.Cmain / 32) + a.Cskip / 32 && conv_x3_eligible(a) && a.x3 && conv_x3_smem_bytes(a, t) <= CONV_X3_MAX_LDS;
-            const bool win_ok = t.NW == 80 && (t.MT == 1 || t.MT == 2) && (t.NT == 2 || t.NT == 4) && (t.KS == 1 || t.KS == 2 || t.KS == 4) && (t.XM == 0 || t.XM == 1) && conv_win_eligible(a, t.MT, t.NT, t.KS);
-            const bool pw_ok = t.NW == 96 && (t.KS == 1 || t.KS == 2 || t.KS == 4 || t.KS == 6) && (t.XM == 0 || t.XM == 1) && conv_pw_eligible(a, t.MT, t.NT, t.KS);
-            const bool shape_ok = tiled_ok || lin_ok || b3_ok || win_ok || pw_ok ||
-                                  ((t.MT == 1 || t.MT == 2 || t.MT == 4) && (t.NT == 1 || t.NT == 2 || t.NT == 4) &&
-                                   (t.NW == 1 || t.NW == 2 || t.NW == 4 || t.NW == 8 || t.NW == 16) && !(t.NW == 16 && t.MT * t.NT >= 8) &&
-                                   t.KS >= 1 && t.KS <= 16 && (t.KS & (t.KS - 1)) == 0 && (t.XM == 0 || t.XM == 1));
-            if (!shape_ok || (!tiled_ok && !lin_ok && !b3_ok && !win_ok && !pw_ok && t.NW * t.KS > nchunks) || (!lin_ok && !pw_ok && t.KS > 1 && ((size_t)t.KS * a.B * a.Lout * a.N > slab_cap || (a.N & 3))) ||
-                (!b3_ok && !win_ok && !pw_ok && conv_smem_bytes(a, t) > 120 * 1024)) {
-                // (a plain entry that a lin-eligible conv only borrowed stays: it may be its twin's; the new measurement goes under "<key> l")
-                if (lin_fallback) { char kl[192]; snprintf(kl, sizeof kl, "%s l", key); snprintf(key, sizeof key, "%s", kl); }
-                else c->tune_cache.erase(it);
-                it = c->tune_cache.end();
-            }
+        // an entry read from MTV_TUNE_CACHE is only trusted if it is launchable
+        if (it != c->tune_cache.end() && !(conv_tile_runs(a, it->second, slab_cap) && (conv_family(it->second) != CONV_X3 || x3_tuner_offers(a)))) {
+            if (!borrowed) c->tune_cache.erase(it);
+            it = c->tune_cache.end();
         }
         if (it == c->tune_cache.end()) {
             const int nchunks = a.ntaps * (a.Cmain / 16) + a.Cskip / 16;
@@ -1332,6 +1294,27 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
             const double abytes = 4.0 * a.B * ((double)a.Lsrc * a.Cmain + (double)a.Lskip * a.Cskip + (double)a.Lout * a.N);
             ConvTile best = op->t;
             float best_ms = 1e30f;
+            // One candidate, timed cold: the caches (32 MB L2 + 256 MB MALL) are flushed before every timed launch, because in the real step
+            // a layer's weights were last touched 0.5 GB ago.  Median of `nsamp` samples: a single slow sample -- clock ramp, a neighbour's
+            // traffic -- must not decide the plan.  A tie keeps the earlier candidate.
+            auto time_tile = [&](const ConvTile& t) -> int {
+                float samp[16];
+                HIPCHK(run(t));
+                for (int w = 0; w < nsamp; ++w) {
+                    HIPCHK(hipMemsetAsync(c->flush, w, c->flush_bytes, s));
+                    HIPCHK(hipEventRecord(e0, s));
+                    HIPCHK(run(t));
+                    HIPCHK(hipEventRecord(e1, s));
+                    HIPCHK(hipEventSynchronize(e1));
+                    HIPCHK(hipEventElapsedTime(&samp[w], e0, e1));
+                }
+                std::sort(samp, samp + nsamp);
+                if (samp[nsamp / 2] < best_ms) {
+                    best_ms = samp[nsamp / 2];
+                    best = t;
+                }
+                return MTV_OK;
+            };
             for (auto& mn : cand) {
                 const int MT = mn[0], NT = mn[1];
                 if (NT > 1 && NT * 8 >= a.N) continue;
@@ -1348,26 +1331,7 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
                             if (XM == 1 && (wbytes < 2.0 * abytes || (long)((a.N + 16 * NT - 1) / (16 * NT)) * KS < 8)) continue;
                             const ConvTile t{MT, NT, NW, KS, XM};
                             if (conv_smem_bytes(a, t) > 120 * 1024) continue;
-                            // cold timing: the caches (32 MB L2 + 256 MB MALL) are flushed before every timed
-                            // launch, because in the real step a layer's weights were last touched 0.5 GB ago
-                            // (median of `nsamp` samples: a single slow sample -- clock ramp, a neighbour's
-                            // traffic -- must not decide the plan)
-                            float samp[16];
-                            HIPCHK(run(t));
-                            for (int w = 0; w < nsamp; ++w) {
-                                HIPCHK(hipMemsetAsync(c->flush, w, c->flush_bytes, s));
-                                HIPCHK(hipEventRecord(e0, s));
-                                HIPCHK(run(t));
-                                HIPCHK(hipEventRecord(e1, s));
-                                HIPCHK(hipEventSynchronize(e1));
-                                HIPCHK(hipEventElapsedTime(&samp[w], e0, e1));
-                            }
-                            std::sort(samp, samp + nsamp);
-                            const float med = samp[nsamp / 2];
-                            if (med < best_ms) {
-                                best_ms = med;
-                                best = t;
-                            }
+                            if (const int rc = time_tile(t)) return rc;
                         }
                     }
                 }
@@ -1382,26 +1346,11 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
                     if (mn[1] == 8 && a.N < 256) continue;
                     if ((long)a.B * ((a.Lout + 32 * t.MT - 1) / (32 * t.MT)) * ((a.N + 32 * t.NT - 1) / (32 * t.NT)) < 128) continue;
                     if (conv_smem_bytes(a, t) > 120 * 1024) continue;
-                    float samp[16];
-                    HIPCHK(run(t));
-                    for (int w = 0; w < nsamp; ++w) {
-                        HIPCHK(hipMemsetAsync(c->flush, w, c->flush_bytes, s));
-                        HIPCHK(hipEventRecord(e0, s));
-                        HIPCHK(run(t));
-                        HIPCHK(hipEventRecord(e1, s));
-                        HIPCHK(hipEventSynchronize(e1));
-                        HIPCHK(hipEventElapsedTime(&samp[w], e0, e1));
-                    }
-                    std::sort(samp, samp + nsamp);
-                    if (samp[nsamp / 2] < best_ms) {
-                        best_ms = samp[nsamp / 2];
-                        best = t;
-                    }
+                    if (const int rc = time_tile(t)) return rc;
                 }
             }
             // the split-bf16 kernels (conv_x3.hip) for large token counts: the timed launch is the elementwise pass + the GEMM
-            // (not for the one-clip step at R = 32, the metric's workload: it stays on the exact-f32 instruction throughout)
-            if ((long)a.B * a.Lout >= X3_MIN_ROWS && !(a.B == 1 && a.Lout <= 2048) && conv_x3_eligible(a) && a.x3) {
+            if ((long)a.B * a.Lout >= X3_MIN_ROWS && x3_tuner_offers(a) && conv_x3_eligible(a) && a.x3) {
                 static const int tb[][2] = {{4, 2}, {2, 2}, {4, 1}, {2, 1}, {8, 2}, {8, 1}, {4, 4}};
                 const int nch32 = a.ntaps * (a.Cmain / 32) + a.Cskip / 32;
                 for (auto& mn : tb)
@@ -1413,21 +1362,7 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
                         // K slices only while the tiles alone leave CUs idle, and never fewer than 6 chunks per slice
                         if (KS > 1 && (ntile * (KS / 2) >= 256 || nch32 / KS < 6 || (size_t)KS * a.B * a.Lout * a.N > slab_cap)) continue;
                         if (conv_x3_smem_bytes(a, t) > CONV_X3_MAX_LDS) continue;
-                        float samp[16];
-                        HIPCHK(run(t));
-                        for (int w = 0; w < nsamp; ++w) {
-                            HIPCHK(hipMemsetAsync(c->flush, w, c->flush_bytes, s));
-                            HIPCHK(hipEventRecord(e0, s));
-                            HIPCHK(run(t));
-                            HIPCHK(hipEventRecord(e1, s));
-                            HIPCHK(hipEventSynchronize(e1));
-                            HIPCHK(hipEventElapsedTime(&samp[w], e0, e1));
-                        }
-                        std::sort(samp, samp + nsamp);
-                        if (samp[nsamp / 2] < best_ms) {
-                            best_ms = samp[nsamp / 2];
-                            best = t;
-                        }
+                        if (const int rc = time_tile(t)) return rc;
                     }
             }
             // the window-staged 3x3 kernel (deep.hip, k_conv_win): GroupNorm / FiLM / SiLU once per element, all taps from LDS
@@ -1444,21 +1379,7 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
                     const long ntile = (long)a.B * ((a.Lout + 16 * t.MT - 1) / (16 * t.MT)) * (a.N / (16 * t.NT));
                     if (ntile * KS < 64) continue;
                     if (KS > 1 && (ntile * KS > 256 || a.Cmain / 16 / KS < 3 || (size_t)KS * a.B * a.Lout * a.N > slab_cap)) continue;
-                    float samp[16];
-                    HIPCHK(run(t));
-                    for (int w = 0; w < nsamp; ++w) {
-                        HIPCHK(hipMemsetAsync(c->flush, w, c->flush_bytes, s));
-                        HIPCHK(hipEventRecord(e0, s));
-                        HIPCHK(run(t));
-                        HIPCHK(hipEventRecord(e1, s));
-                        HIPCHK(hipEventSynchronize(e1));
-                        HIPCHK(hipEventElapsedTime(&samp[w], e0, e1));
-                    }
-                    std::sort(samp, samp + nsamp);
-                    if (samp[nsamp / 2] < best_ms) {
-                        best_ms = samp[nsamp / 2];
-                        best = t;
-                    }
+                    if (const int rc = time_tile(t)) return rc;
                 }
             }
             // the 1x1 kernel of the large levels (deep.hip, k_conv_pw): rows normalised once into LDS, 8 waves side by side along N
@@ -1475,51 +1396,9 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
                         // (the XCD-aware block order only where the column groups tile the 8 XCDs and the weights dwarf the rows: measured -0.5 ... -0.8 us per
                         // launch at [128 x 1536, K = 512], +0.3 ... +0.8 at 512 tokens -- profiles/r06_conv_pw_xcd_order_ab.txt)
                         if (XM == 1 && (((a.N + cols - 1) / cols) % 8 || (long)a.N < 8L * a.B * a.Lout)) continue;
-                        float samp[16];
-                        HIPCHK(run(t));
-                        for (int w = 0; w < nsamp; ++w) {
-                            HIPCHK(hipMemsetAsync(c->flush, w, c->flush_bytes, s));
-                            HIPCHK(hipEventRecord(e0, s));
-                            HIPCHK(run(t));
-                            HIPCHK(hipEventRecord(e1, s));
-                            HIPCHK(hipEventSynchronize(e1));
-                            HIPCHK(hipEventElapsedTime(&samp[w], e0, e1));
-                        }
-                        std::sort(samp, samp + nsamp);
-                        if (samp[nsamp / 2] < best_ms) {
-                            best_ms = samp[nsamp / 2];
-                            best = t;
-                        }
+                        if (const int rc = time_tile(t)) return rc;
                       }
                     }
-            }
-            // the lean 1x1 kernel (lin.hip): wave tile 16 MT x 16 NT, NWV waves side by side along N, whole K per wave
-            // (offered only with MTV_TUNE_LIN=1: in the step's graph its picks measured slower than k_conv's / k_conv_pw's on the same
-            // shapes -- profiles/r04_per_op_rocprof.txt -- although they win the tuner's cold, isolated timing)
-            static const bool tune_lin = getenv("MTV_TUNE_LIN") != nullptr;
-            if (tune_lin && conv_lin_eligible(a)) {
-                for (int MT = 1; MT <= 2; ++MT)
-                    for (int NT = 1; NT <= 4; NT *= 2)
-                        for (int NWV = 1; NWV <= 4; NWV *= 2) {
-                            if (MT == 2 && a.Lout < 32) continue;
-                            if (16 * NT * NWV > a.N && NWV > 1) continue;           // wider than the layer
-                            const ConvTile t{MT, NT, 64, NWV, 0};
-                            float samp[16];
-                            HIPCHK(run(t));
-                            for (int w = 0; w < nsamp; ++w) {
-                                HIPCHK(hipMemsetAsync(c->flush, w, c->flush_bytes, s));
-                                HIPCHK(hipEventRecord(e0, s));
-                                HIPCHK(run(t));
-                                HIPCHK(hipEventRecord(e1, s));
-                                HIPCHK(hipEventSynchronize(e1));
-                                HIPCHK(hipEventElapsedTime(&samp[w], e0, e1));
-                            }
-                            std::sort(samp, samp + nsamp);
-                            if (samp[nsamp / 2] < best_ms) {
-                                best_ms = samp[nsamp / 2];
-                                best = t;
-                            }
-                        }
             }
             it = c->tune_cache.emplace(key, best).first;
             tune_cache_append(key, best);
@@ -2348,46 +2227,22 @@ int mtv_debug_attention_qb(int mode) {
 }
 
 int mtv_debug_force_b3(int mt, int nt, int ks) {
-    if (mt == 0) { g_force_b3[0] = 0; return MTV_OK; }
-    if (!(ks == 1 || ks == 2 || ks == 4 || ks == 8)) return fail(MTV_ERR_INVALID, "K slices must be 1, 2, 4 or 8");
-    if (!x3_tile_exists(mt, nt)) return fail(MTV_ERR_INVALID, "no k_conv_x3<MT, NT> of that shape (4,2 8,2 4,4 2,2 4,1 2,1 8,1)");
-    g_force_b3[0] = mt; g_force_b3[1] = nt; g_force_b3[2] = ks;
-    return MTV_OK;
-}
-
-int mtv_debug_force_lin(int mt, int nt, int nwv) {
-    if (mt == 0) { g_force_lin[0] = 0; return MTV_OK; }
-    if (!((mt == 1 || mt == 2) && (nt == 1 || nt == 2 || nt == 4) && (nwv == 1 || nwv == 2 || nwv == 4))) return fail(MTV_ERR_INVALID, "k_lin tile must be {1,2} x {1,2,4} x {1,2,4}");
-    g_force_lin[0] = mt; g_force_lin[1] = nt; g_force_lin[2] = nwv;
-    return MTV_OK;
+    return force_set(g_force_b3, mt, nt, ks) ? MTV_OK : fail(MTV_ERR_INVALID, "no k_conv_x3<MT, NT> of that shape (4,2 8,2 4,4 2,2 4,1 2,1 8,1), or K slices not 1, 2, 4 or 8");
 }
 
 int mtv_debug_force_pw(int mt, int ntw) { return mtv_debug_force_pw_waves(mt, ntw, 1); }
 
 int mtv_debug_force_pw_waves(int mt, int ntw, int waves) {
-    if (mt == 0) { g_force_pw[0] = 0; return MTV_OK; }
-    if (waves == 8) waves = 1;
-    if (!((mt == 1 || mt == 2) && (ntw == 1 || ntw == 2)) || !(waves == 1 || (ntw == 1 && (waves == 2 || waves == 4 || waves == 6))))
-        return fail(MTV_ERR_INVALID, "k_conv_pw tile must be {1, 2} x {1, 2} with 8 multiplying waves, or {1, 2} x 1 with 6 / 4 / 2");
-    g_force_pw[0] = mt; g_force_pw[1] = ntw; g_force_pw[2] = waves;
-    return MTV_OK;
+    return force_set(g_force_pw, mt, ntw, waves) ? MTV_OK : fail(MTV_ERR_INVALID, "k_conv_pw tile must be {1, 2} x {1, 2} with 8 multiplying waves, or {1, 2} x 1 with 6 / 4 / 2");
 }
 
 int mtv_debug_force_win_ks(int mt, int nt, int ks) {
-    if (mt == 0) { g_force_win[0] = 0; return MTV_OK; }
-    if (!((mt == 1 || mt == 2) && (nt == 2 || nt == 4))) return fail(MTV_ERR_INVALID, "k_conv_win tile must be 1x2, 1x4, 2x2 or 2x4");
-    if (ks != 1 && ks != 2 && ks != 4) return fail(MTV_ERR_INVALID, "k_conv_win runs 1, 2 or 4 K slices");
-    g_force_win[0] = mt; g_force_win[1] = nt; g_force_win[2] = ks;
-    return MTV_OK;
+    return force_set(g_force_win, mt, nt, ks) ? MTV_OK : fail(MTV_ERR_INVALID, "k_conv_win tile must be 1x2, 1x4, 2x2 or 2x4, with 1, 2 or 4 K slices");
 }
 int mtv_debug_force_win(int mt, int nt) { return mtv_debug_force_win_ks(mt, nt, 1); }
 
 int mtv_debug_force_lds(int wm, int wn) {
-    if (wm == 0) { g_force_wm = 0; return MTV_OK; }
-    if (!((wm == 2 || wm == 4) && (wn == 2 || wn == 4 || wn == 8))) return fail(MTV_ERR_INVALID, "wave tile must be 2 or 4 by 2, 4 or 8");
-    g_force_wm = wm;
-    g_force_wn = wn;
-    return MTV_OK;
+    return force_set(g_force_lds, wm, wn, 1) ? MTV_OK : fail(MTV_ERR_INVALID, "wave tile must be 2 or 4 by 2, 4 or 8");
 }
 
 int mtv_set_eager(mtv_ctx* c, int eager) {

@@ -49,7 +49,7 @@ struct WSlot {
     int ld;         // ROLE_CONV: leading dimension (padded output channels)
     bool loaded;
     int aux = 0;    // ROLE_QKV_HEADS: head dim; ROLE_REPEAT: repeat count
-    float* dst2 = nullptr;   // ROLE_CONV, 1x1 only: a second copy in the checkpoint's own layout [N][C] (k_lin, lin.hip)
+    float* dst2 = nullptr;   // ROLE_CONV, 1x1 only: a second copy in the checkpoint's own layout [N][C] (DeepBlockArgs::Wq / Wp, block.hip)
     float* dst3 = nullptr;   // ROLE_CONV, 1x1 only, N and C multiples of 16: a third copy in k_conv_pw's lane-linear layout (ConvArgs::Wpk)
 };
 
@@ -319,4 +319,4 @@ constexpr long X3_MIN_ROWS = 1024;
 bool x3_wanted(long rows);                                  // plan.hip: offer this conv to the split-bf16 kernels?
 int check_ready(mtv_ctx* c, int batch);                     // (also refreshes the split-bf16 weight copies after a weight load)
 int ctx_init_common(mtv_ctx* c);
-void force_lds_tile(const ConvArgs& a, ConvTile* t);    // MTV_FORCE_LDS / MTV_FORCE_LIN testing aids
+void force_family_tile(const ConvArgs& a, ConvTile* t);    // MTV_FORCE_WIN / _PW / _B3 / _LDS and the mtv_debug_force_* testing aids

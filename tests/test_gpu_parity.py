@@ -401,16 +401,6 @@ def test_lds_tiled_conv_kernel_vs_reference_golden(wm, wn):
     _forced("mtv_debug_force_lds", (wm, wn), (0, 0), f"k_conv_lds<{wm},{wn}>", expect)
 
 
-@pytest.mark.parametrize("mt,nt,nwv", [(1, 4, 1), (2, 2, 4)])
-def test_lean_1x1_kernel_vs_reference_golden(mt, nt, nwv):
-    """k_lin (csrc/lin.hip: whole K per wave, weight in the checkpoint's [N][K] layout, epilogue from the accumulators; the tile table
-    selects it for six proj_out shapes of the 8-clip batch and of R = 64) forced onto every eligible qkv / proj_out conv: base UNet eps vs
-    the reference golden at t = 999 / 0 and a ragged 2-clip geometry (row tiles straddling plane boundaries, partial tiles) vs the oracle."""
-    def expect(names):
-        assert sum(f"t{mt},{nt},64,{nwv}]" in n for n in names) >= 60, "the lean kernel was not selected"
-    _forced("mtv_debug_force_lin", (mt, nt, nwv), (0, 0, 0), f"k_lin<{mt},{nt},{nwv}>", expect)
-
-
 def test_bf16_pipe_qk_attention_vs_reference_golden():
     """k_attention<..., QB = 1> (csrc/kernels.hip: QK^T on v_mfma_f32_16x16x32_bf16 through a three-term split of q and k --
     d = 16: two 16-wide products per instruction; PV unchanged on the f32 instruction) switched on for EVERY 8-wave attention
