@@ -18,3 +18,9 @@ BASE_UNET_CONFIG = dict(  # MToV/configs/latent-diffusion/base.yaml:27-38
     num_res_blocks=2, channel_mult=[1, 2, 4, 4], num_heads=8, use_scale_shift_norm=True,
     resblock_updown=True, cond_model=False,
 )
+
+LONGVID_UNET_CONFIG = dict(  # MToV/configs/latent-diffusion/base_longvid.yaml:28-39: head dims 32 / 64 / 128 / 128, 1024-channel deep levels
+    image_size=32, in_channels=4, out_channels=4, model_channels=256, attention_resolutions=[4, 2, 1],
+    num_res_blocks=2, channel_mult=[1, 2, 4, 4], num_heads=8, use_scale_shift_norm=True,
+    resblock_updown=True, cond_model=True,
+)

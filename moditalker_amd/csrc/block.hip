@@ -627,6 +627,7 @@ bool deep_block_configure(DeepBlockArgs& a, int force_cl, int force_rq, int max_
     if (a.B < 1 || a.H < 1 || a.L < 1 || a.L > 128 || a.C % a.H || (a.C & 15)) return false;
     if (a.H > 8 || (a.H & (a.H - 1))) return false;                      // the heads are the output slabs: 1, 2, 4 or 8
     const int d = a.C / a.H;
+    // (d = 128, the long-video model's deep levels: not here on purpose -- those blocks take the three-launch form, fin + qkv + k_deep_attn<128>, at 32 tokens too)
     if (d != 16 && d != 32 && d != 64) return false;
     if (a.gs < 1 || a.C % a.gs) return false;
     if (!(a.x.ks == 1 || a.x.ks == 2 || a.x.ks == 4 || a.x.ks == 8)) return false;

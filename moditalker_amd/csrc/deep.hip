@@ -820,6 +820,12 @@ __device__ __forceinline__ float deep_swap_max32(float x) {
 // rows.  Then D = attention rows x Wp[head group rows][column group] on the same MFMA, K split over the waves, summed in LDS.
 // With the packed matrix (DeepAttnArgs::Wpk) the B fragments of a wave's proj tile are requested at kernel entry and stay in registers; with HPW = 1 / NC = 128 (round 7:
 // the [128 x 512] d = 64 blocks) a wave owns a whole tile and stores its output quads from the accumulators (profiles/r07_deep_attn_heads.md).
+// D = 128 (the long-video model's deep levels): one head and one query tile per workgroup, always.  At 128 keys Ks and V^T are 66 KB each and so are the eight key-part
+// partials, which is more than the 160 KB a workgroup may ask for -- so the partials (Os, and after them the proj partials + completion scratch) lie OVER Ks:
+//   [ Ks | Os : max(kcap x 132, 8 x 16 x 132) ][ Vt 128 x (kcap + 4) ][ Qs 16 x 132 ][ Att 16 x 136 ][ Wt NC x 132, staged form only ][ ml ][ scratch, NC = 128 only ]
+// = 150 KB at 128 keys with packed weights (153 KB at NC = 128; 158 KB with the staged slice, which fits at NC = 16 only).  Ks is dead once every wave has its S^T tile: one
+// extra barrier between the last S^T and the first parked partial.  A head's K slice of the projection is 8 chunks: two K parts of four at NC = 64, and at NC = 128 the
+// wave that owns a whole tile holds eight B fragments (wreg[8]).  deep_attn_smem is the one statement of this layout for the host.
 template <int D>
 __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
     const int tid = threadIdx.x;
@@ -860,17 +866,18 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
     // bank, the minimum; keys stay contiguous inside a block, so the fragment reads remain 16-byte reads.  Needs whole 32-key groups: an even number of key tiles.
     const int vswz = (nkt & 1) ? 0 : 7;
     const int wswz = ((HPW * D) & 31) ? 0 : 7;                // ... and of the transposed proj slice Wt[column][k] (whole 32-k groups)
+    constexpr bool OVK = D == 128;                            // key-part partials over Ks (above)
+    constexpr int OSF = 8 * 16 * (D + 4) > 8 * 16 * 20 + DEEP_FIN_FLOATS ? 8 * 16 * (D + 4) : 8 * 16 * 20 + DEEP_FIN_FLOATS;
     float* const Ks = smem;                                   // [kcap][KSTR]
-    float* const Vt = Ks + a.kcap * KSTR;                     // [D][VSTR]
+    float* const Vt = Ks + (OVK && a.kcap * KSTR < OSF ? OSF : a.kcap * KSTR);      // [D][VSTR]
     float* const Qs = Vt + D * VSTR;                          // [QR][KSTR]
     float* const Att = Qs + QR * KSTR;                        // [QR][AS]: normalised attention rows of the head group
     // packed weights (DeepAttnArgs::Wpk): no Wt.  kparts == 1 (NC = 128: launch_deep_attn admits it with packed weights only): every wave owns a whole proj tile -- no
     // cross-wave sum, the epilogue runs from the accumulators, the completion scratch gets LDS of its own (it is written before the first barrier)
     const bool pk = a.Wpk != nullptr;
     float* const Wt = Att + QR * AS;                          // [NC][WS]: proj slice, transposed (k contiguous)
-    float* const Os = Wt + (pk ? 0 : NC * WS);                // [8 waves][16 queries][D + 4]: key-part partials (then proj partials)
-    constexpr int OSF = 8 * 16 * (D + 4) > 8 * 16 * 20 + DEEP_FIN_FLOATS ? 8 * 16 * (D + 4) : 8 * 16 * 20 + DEEP_FIN_FLOATS;
-    float* const ml = Os + OSF;                               // [8 waves][16 queries][2]: (m, l) of the key parts
+    float* const Os = OVK ? Ks : Wt + (pk ? 0 : NC * WS);     // [8 waves][16 queries][D + 4]: key-part partials (then proj partials)
+    float* const ml = OVK ? Wt + (pk ? 0 : NC * WS) : Os + OSF;      // [8 waves][16 queries][2]: (m, l) of the key parts
     const int qt = QT == 2 ? (wave & 1) : 0, kp = QT == 2 ? (wave >> 1) : wave;      // this wave: query tile, key part
     const int KPS = 8 / QT;                                   // key parts (= the stride of a wave's key tiles)
     // proj phase: [QR rows][NC cols] = Att [QR][kw] x Wp slice; wave -> (tile, K part)
@@ -883,7 +890,8 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
     const bool direct = kparts == 1;
     float* const fscratch = direct ? ml + 8 * 16 * 2 : Os + 8 * 16 * 20;     // completion scratch (not direct: past the proj partials -- the key-part partials that lay there are dead by then)
     // ---- proj slice requested first: it depends on nothing (held in registers until the first barrier; packed: until the proj phase)
-    f32x4 wreg[4];                                            // (NC = 64: up to four quads per thread; packed: the B fragments of up to four chunks)
+    constexpr int WR = D == 128 ? 8 : 4;                      // (D = 128, NC = 128: the eight chunks of a head's K slice)
+    f32x4 wreg[WR];                                           // (NC = 64: up to four quads per thread; packed: the B fragments of up to four chunks)
     const int wu_n = (kw * wq + DEEP_NTH - 1) / DEEP_NTH;     // (uniform)
     {
         // Four loads per thread in either form, the ADDRESS chosen by the form -- no branch, no fill value: a register that one path loads and another path writes makes
@@ -892,7 +900,7 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
         const float* wpb = a.Wpk + (((size_t)(cg * nct + ct) * (C >> 4) + hg * kchunks + (kpart * cpp < kchunks ? kpart * cpp : 0)) * 64 + lane) * 4;
         const float* wb = a.Wp + (size_t)(hg * kw) * a.ldw + cg * NC;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < WR; ++u) {
             const int e = tid + DEEP_NTH * u;
             const int kr = e >> wq_sh, cq = e & (wq - 1);
             const float* ps = wb + (size_t)(kr < kw ? kr : 0) * a.ldw + 4 * cq;
@@ -953,14 +961,17 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
             *reinterpret_cast<f32x4*>(Qs + qr * KSTR + 4 * qd) = qregl * (a.scale * LOG2E);
         }
     };
-    static_assert(32 * QPR <= DEEP_NTH, "one Q quad per thread");
+    static_assert((D == 128 ? 16 : 32) * QPR <= DEEP_NTH, "one Q quad per thread (D = 128: one query tile -- launch_deep_attn)");
     issue(0);
     DEEP_STAMP(1);
-    for (int hh = 0; hh < HPW; ++hh) {
+    // (D = 128: ONE head, known to the compiler -- as a loop body the parking addresses of eight items per thread are loop invariants that stay live across the
+    //  whole attention, which costs scratch)
+    const int nhh = OVK ? 1 : HPW;
+    for (int hh = 0; hh < nhh; ++hh) {
         park();
         if (hh == 0) DEEP_STAMP(2);
         if (hh == 1) DEEP_STAMP(10);
-        if (hh + 1 < HPW) issue(hh + 1);
+        if (hh + 1 < nhh) issue(hh + 1);
         if (hh == 0 && direct && tg) {                       // (the ticket was requested before K / V: it has landed with them)
             if (tid == 0) *reinterpret_cast<unsigned*>(fscratch) = (unsigned)(early >> __builtin_ctz(a.nhg)) + 1u;
             if (hg == 0) {
@@ -992,10 +1003,11 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
         }
         const int qtok = q0 + 16 * qt + j;                     // this lane's query (column j)
         const int qpl = qtok >= b2 ? 2 : (qtok >= b1 ? 1 : 0);
-        f32x4 st[2];
+        constexpr int NW = D == 128 ? 1 : 2;                  // key tiles per wave (one query tile: kp + 8 is always past the end; D = 128 is never anything else)
+        f32x4 st[NW];
         float m = -INFINITY;
 #pragma unroll
-        for (int w = 0; w < 2; ++w) {
+        for (int w = 0; w < NW; ++w) {
             const int kt = kp + KPS * w;
             f32x4 sacc = {0.f, 0.f, 0.f, 0.f};
             if (kt < nkt) {
@@ -1021,7 +1033,7 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
         const bool live = m != -INFINITY;                    // (a key part may hold only keys of other planes)
         float lsum = 0.f;
 #pragma unroll
-        for (int w = 0; w < 2; ++w)
+        for (int w = 0; w < NW; ++w)
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 const float pz = live ? __builtin_amdgcn_exp2f(st[w][rr] - m) : 0.f;
@@ -1034,7 +1046,7 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
 #pragma unroll
         for (int o = 0; o < NDT; ++o) oacc[o] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int w = 0; w < 2; ++w) {
+        for (int w = 0; w < NW; ++w) {
             const int kt = kp + KPS * w;
             if (kt < nkt) {
 #pragma unroll
@@ -1046,6 +1058,7 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
             }
         }
         // park (m, l, O^T) of this key part: O^T lane (query j, group g) reg r = d index 16 o + 4 g + r
+        if constexpr (OVK) __syncthreads();                  // (the partials lie over Ks: every wave has read its K fragments)
         {
             float* op = Os + ((size_t)wave * 16 + j) * (D + 4) + 4 * g;
 #pragma unroll
@@ -1088,7 +1101,7 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
     f32x4 pacc = {0.f, 0.f, 0.f, 0.f};
     if (pk) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < WR; ++u) {
             const int cc = kpart * cpp + u;
             if (u < cpp && cc < kchunks) {                      // (uniform)
                 const f32x4 af = *reinterpret_cast<const f32x4*>(Att + (16 * rt + j) * AS + 16 * cc + 4 * g);
@@ -2130,6 +2143,7 @@ hipError_t deep_init_attrs() {
         if (e != hipSuccess) return e;
     }
     const void* fa[] = {reinterpret_cast<const void*>(&k_deep_attn<16>), reinterpret_cast<const void*>(&k_deep_attn<32>), reinterpret_cast<const void*>(&k_deep_attn<64>),
+                        reinterpret_cast<const void*>(&k_deep_attn<128>),
                         reinterpret_cast<const void*>(&k_conv_win<1, 4>), reinterpret_cast<const void*>(&k_conv_win<1, 2>),
                         reinterpret_cast<const void*>(&k_conv_win<2, 2>), reinterpret_cast<const void*>(&k_conv_win<2, 4>),
                         reinterpret_cast<const void*>(&k_conv_pw<1, 1, 8>), reinterpret_cast<const void*>(&k_conv_pw<1, 2, 8>),
@@ -2163,19 +2177,22 @@ static size_t deep_attn_smem(const DeepAttnArgs& a, int D, bool with_wt = false)
     const int QR = 16 * (a.QT == 1 ? 1 : 2);
     const int wt = (a.Wpk && !with_wt) ? 0 : a.NC * WS;
     const int fsc = a.NC == 128 ? DEEP_FIN_FLOATS : 0;       // one tile per wave: completion scratch of its own
-    return (size_t)(a.kcap * KSTR + D * VSTR + QR * KSTR + QR * AS + wt + os + 8 * 16 * 2 + fsc) * 4;
+    const int ks = a.kcap * KSTR;
+    const int kos = D == 128 ? (ks > os ? ks : os) : ks + os;        // D = 128: the partials lie over Ks (k_deep_attn)
+    return (size_t)(kos + D * VSTR + QR * KSTR + QR * AS + wt + 8 * 16 * 2 + fsc) * 4;
 }
 
 bool deep_attn_configure(DeepAttnArgs& a) {
     if (a.H < 1 || a.C % a.H || a.L < 1 || a.L > 128 || (a.C & 15)) return false;
     const int d = a.C / a.H;
-    if (d != 16 && d != 32 && d != 64) return false;
+    if (d != 16 && d != 32 && d != 64 && d != 128) return false;
     a.kcap = (a.L + 15) / 16 * 16;
     // round 6: ONE query tile per workgroup x 8 key parts, proj slices up to 64 columns -- at [128 x 512] 8 query groups x 4 head groups x 8 column groups = the same
     // 256 workgroups, each recomputing half the attention (1.9482 -> 1.9385 ms per step same-box, profiles/r06_deep_attn_query_tile_ab.txt).  MTV_DEEP_ATTN_QT=2: round 4's
     // 2 query tiles x 4 key parts, 16- / 32-column slices
     static const int env_qt = getenv("MTV_DEEP_ATTN_QT") ? atoi(getenv("MTV_DEEP_ATTN_QT")) : 1;
     a.QT = env_qt == 2 ? 2 : 1;
+    if (d == 128 && a.QT != 1) return false;                 // 128-wide heads: one Q quad per thread means one query tile
     a.nqg = (a.L + 16 * a.QT - 1) / (16 * a.QT);
     // ONE head per workgroup, 128-column proj slices from the packed matrix (HPW = 1, NC = 128; QT = 1 only): at [128 x 512] d = 64 8 query groups x 8 head groups x 4
     // column groups = the same 256 workgroups, each loading ONE head's K / V (64 KB instead of 128) and the attention of a (head, query tile) computed 4 times instead of
@@ -2187,7 +2204,9 @@ bool deep_attn_configure(DeepAttnArgs& a) {
     if (form != 2 && a.QT == 1 && a.Wpk && a.C % 128 == 0 && a.H <= 8 && !(a.H & (a.H - 1))) {
         a.HPW = 1; a.NC = 128; a.nhg = a.H; a.ncg = a.C / 128;
         const long wgs = (long)a.B * a.nqg * a.nhg * a.ncg;
-        const bool rule = d == 64 && a.L > 112 && a.H == 8 && wgs >= 128 && wgs <= 256;
+        // 128-wide heads are one head per workgroup in any form (hpw d <= 128): the 128-column slice halves the workgroups that recompute a (head, query tile) against
+        // 64 columns, at the same 8 slabs -- taken wherever it still fills half the chip (long-video model: 512 workgroups at 128 tokens, 128 at 32)
+        const bool rule = d == 128 ? wgs >= 128 : (d == 64 && a.L > 112 && a.H == 8 && wgs >= 128 && wgs <= 256);
         if ((form == 1 || rule) && deep_attn_smem(a, d) <= 160 * 1024) return true;
     }
     // head group = K slice of the projection = an output slab: as few slabs as the grid allows (consumers re-read every slab)
@@ -2198,7 +2217,8 @@ bool deep_attn_configure(DeepAttnArgs& a) {
             if ((hpw * d) * (nc / 4) > (nc == 64 ? 4 : 2) * DEEP_NTH) continue;             // proj slice: two (NC = 64: four) 16-byte quads per thread
             a.HPW = hpw; a.NC = nc; a.nhg = a.H / hpw; a.ncg = a.C / nc;
             if (a.nhg > 8 || (a.nhg & (a.nhg - 1))) continue;
-            if (deep_attn_smem(a, d, true) > 160 * 1024) continue;
+            // (d = 128: the staged slice fits beside the tiles at 16 columns only -- wider slices exist on packed weights alone, so there the caller's copy does decide)
+            if (deep_attn_smem(a, d, d != 128) > 160 * 1024) continue;
             const long wgs = (long)a.B * a.nqg * a.nhg * a.ncg;
             if (wgs >= 128) return true;                                     // enough to occupy half the chip: take the fewest slabs
         }
@@ -2220,11 +2240,12 @@ hipError_t launch_deep_attn(const DeepAttnArgs& a0, hipStream_t s) {
     a.inv_nslots = 1.0f / (float)a.nslots;
     if (a.QT != 1 && a.QT != 2) return hipErrorInvalidValue;
     const bool h1 = a.NC == 128;                             // one proj tile per wave: packed weights, one query tile, the K slice in four chunks at most
-    if (h1 && !(a.QT == 1 && a.HPW == 1 && a.Wpk && d <= 64 && a.C % 128 == 0)) return hipErrorInvalidValue;
+    if (h1 && !(a.QT == 1 && a.HPW == 1 && a.Wpk && d <= 128 && a.C % 128 == 0)) return hipErrorInvalidValue;
+    if (d == 128 && !(a.QT == 1 && a.HPW == 1)) return hipErrorInvalidValue;       // k_deep_attn<128>: one query tile, one head (the partials lie over Ks)
     if (!h1 && a.NC != 16 && a.NC != 32 && !(a.NC == 64 && a.QT == 1)) return hipErrorInvalidValue;
     {   // packed B fragments live in four registers quads per lane: chunks per K part <= 4 (every form deep_attn_configure makes), else the LDS-staged slice
         const int kparts = 8 / (a.QT * (a.NC >> 4)), kchunks = (a.HPW * d) >> 4;
-        if ((a.C & 15) || (kchunks + kparts - 1) / kparts > 4) { if (h1) return hipErrorInvalidValue; a.Wpk = nullptr; }
+        if ((a.C & 15) || (kchunks + kparts - 1) / kparts > (d == 128 ? 8 : 4)) { if (h1) return hipErrorInvalidValue; a.Wpk = nullptr; }
     }
     const size_t smem = deep_attn_smem(a, d);
     if (smem > 160 * 1024 || !(a.res.ks >= 1 && a.res.ks <= 8)) return hipErrorInvalidValue;
@@ -2232,6 +2253,7 @@ hipError_t launch_deep_attn(const DeepAttnArgs& a0, hipStream_t s) {
     if (d == 16) hipLaunchKernelGGL((k_deep_attn<16>), grid, dim3(DEEP_NTH), smem, s, a);
     else if (d == 32) hipLaunchKernelGGL((k_deep_attn<32>), grid, dim3(DEEP_NTH), smem, s, a);
     else if (d == 64) hipLaunchKernelGGL((k_deep_attn<64>), grid, dim3(DEEP_NTH), smem, s, a);
+    else if (d == 128) hipLaunchKernelGGL((k_deep_attn<128>), grid, dim3(DEEP_NTH), smem, s, a);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -506,6 +506,32 @@ static int do_attn(bool timing) {
     printf("%s (%d failing)\n", bad ? "ATTN CHECK FAILED" : "ATTN CHECK OK", bad);
     return bad;
 }
+// k_deep_attn<128> (the long-video model's deep levels: one head per workgroup, key-part partials over Ks).  Every case in all three forms -- all exist at d = 128: the
+// LDS-staged slice (16 columns: the only width that fits beside the tiles), packed weights with the rule's slice width, packed weights with a 128-column slice.
+static int do_attn128(bool timing) {
+    int bad = 0;
+    for (int form : {0, 2, 1}) {
+        bad += run_attn(8, 4, 256, 2, 1, 1, false, form);        // 128 tokens: a full key range, 8 key tiles
+        bad += run_attn(8, 4, 256, 2, 1, 8, false, form);
+        bad += run_attn(8, 4, 256, 2, 0, 1, false, form);        // per plane: the border 64 | 96 inside a key part
+        bad += run_attn(8, 4, 256, 2, 0, 8, false, form);
+        bad += run_attn(4, 2, 256, 2, 1, 1, false, form);        // 32 tokens: two key tiles (V^T swizzle on); per plane: 16 | 8 | 8, one key tile for the first query group
+        bad += run_attn(4, 2, 256, 2, 0, 1, false, form);
+        bad += run_attn(6, 3, 256, 2, 0, 1, false, form);        // ragged planes 36 | 18 | 18: a query tile across a plane border, odd key-tile counts
+        bad += run_attn(3, 1, 128, 1, 0, 1, false, form);        // 15 tokens: less than one key tile, a single slab
+        bad += run_attn(4, 2, 256, 2, 1, 1, false, form, 2);     // two clips
+        bad += run_attn(8, 4, 1024, 8, 1, 1, timing, form);      // the long-video product shape: 8 slabs
+    }
+    {
+        DeepAttnArgs a{};
+        a.B = 1; a.L = 128; a.C = 1024; a.H = 8; a.r = 8; a.t = 4; a.whole = 1;
+        a.Wpk = reinterpret_cast<const float*>(&a);             // (configure only asks whether a packed copy exists)
+        if (deep_attn_configure(a)) printf("product shape [128 x 1024] d128: the rule picks HPW%d NC%d -> %d slabs, %d workgroups\n", a.HPW, a.NC, a.nhg, a.ncg * a.B * a.nqg * a.nhg);
+        else { printf("product shape [128 x 1024] d128: not configurable\n"); ++bad; }
+    }
+    printf("%s (%d failing)\n", bad ? "ATTN128 CHECK FAILED" : "ATTN128 CHECK OK", bad);
+    return bad;
+}
 
 
 // ---------------------------------------------------------------------------------------------------------------- k_deep_block
@@ -878,7 +904,8 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (argc >= 2 && !strcmp(argv[1], "attn")) { CK(deep_init_attrs()); return do_attn(argc >= 3); }
+    if (argc >= 2 && !strcmp(argv[1], "attn128")) { CK(deep_init_attrs()); return do_attn128(argc >= 3); }
     if (argc >= 2 && !strcmp(argv[1], "block")) { CK(deep_block_init_attrs()); return do_block(argc >= 3); }
-    printf("usage: deep_bench check | chain [nops] [r t] | attn [time]\n");
+    printf("usage: deep_bench check | chain [nops] [r t] | attn [time] | attn128 [time]\n");
     return 1;
 }
