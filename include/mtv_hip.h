@@ -194,24 +194,17 @@ int mtv_debug_attention_qb(int mode);
 int mtv_debug_deep(int mode);
 /* Variants of the deep levels' dataflow, for plans built after this call (testing aid; every variant meets the parity bars, the
  * default is the fastest measured): a bit mask of
- *   MTV_DEEP_OPT_INLAUNCH       a deep tensor that a k_conv / k_pool_down / qkv consumer needs as ONE plain tensor is completed inside
- *                               the producing launch (slab + ticket, last-arriving K slice) instead of by a k_deep_finalize pass;
- *   MTV_DEEP_OPT_SLICED_QKV     the attention blocks' qkv conv K-sliced on k_deep_conv (+ a finalize pass) instead of k_conv;
- *   MTV_DEEP_OPT_UNSLICED_QKV   ... on k_deep_conv with the whole K per workgroup (plain output) where it fits in LDS;
- *   MTV_DEEP_OPT_NO_FUSED_ATTN  k_attention + a proj_out conv instead of the fused k_deep_attn;
+ *   MTV_DEEP_OPT_NO_FUSED_ATTN  k_attention + a proj_out conv instead of the fused k_deep_attn (implies the three-launch form below);
  *   MTV_DEEP_OPT_NO_BLOCK       the three-launch attention block of round 4 (k_deep_finalize + qkv conv + k_deep_attn) instead of the
  *                               one-launch k_deep_block (csrc/block.hip: GroupNorm -> qkv -> attention -> proj_out in one kernel, a
- *                               cluster of workgroups per head, two in-launch hand-offs); the four bits above imply it where they
- *                               change the block's dataflow (they describe the three-launch form);
+ *                               cluster of workgroups per head, two in-launch hand-offs);
  *   MTV_DEEP_OPT_BLOCK_ALL      k_deep_block for EVERY attention block of the deep levels it can run, not only where it measures faster
  *                               (by default: 32-token blocks and [128 x 256]; at [128 x 512] the three-launch form is faster);
  *   MTV_DEEP_OPT_FIN_PASS       a separate k_deep_finalize pass (round 4's default) wherever a consumer needs a deep tensor as ONE plain
  *                               tensor, instead of round 5's completion inside the producing kernel by data-tagged granules;
- * -1 = back to the defaults / the MTV_DEEP_INLAUNCH, MTV_DEEP_QKV, MTV_DEEP_QKV1, MTV_DEEP_NO_ATTN, MTV_DEEP_NO_BLOCK, MTV_DEEP_BLOCK_ALL,
- * MTV_DEEP_FIN_PASS environment variables. */
-#define MTV_DEEP_OPT_INLAUNCH 1
-#define MTV_DEEP_OPT_SLICED_QKV 2
-#define MTV_DEEP_OPT_UNSLICED_QKV 4
+ * -1 = back to the defaults / the MTV_DEEP_NO_ATTN, MTV_DEEP_NO_BLOCK, MTV_DEEP_BLOCK_ALL, MTV_DEEP_FIN_PASS environment variables.
+ * Bits 1, 2 and 4 named three variants that measured slower and are retired (ticket completion inside the producing launch, K-sliced
+ * and un-sliced qkv on k_deep_conv; their measurements stay in profiles/ and in git log): a mask with one of them is MTV_ERR_INVALID. */
 #define MTV_DEEP_OPT_NO_FUSED_ATTN 8
 #define MTV_DEEP_OPT_NO_BLOCK 16
 #define MTV_DEEP_OPT_BLOCK_ALL 32

@@ -148,49 +148,7 @@ __device__ __forceinline__ void stage_slice_ks(const DeepSrc& src, const float* 
 
 
 // ---- in-launch completion (DeepFin): shared by k_deep_conv and k_deep_attn --------------------------------------------------------
-typedef __attribute__((address_space(1))) unsigned long long deep_gu64;
-__device__ __forceinline__ void deep_park_quad(float* dst, const f32x4& v) {          // write-through (sc1) 8-byte stores
-    deep_gu64* d = (deep_gu64*)(unsigned long long)dst;
-    __hip_atomic_store(d, ((unsigned long long)__float_as_uint(v[1]) << 32) | __float_as_uint(v[0]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(d + 1, ((unsigned long long)__float_as_uint(v[3]) << 32) | __float_as_uint(v[2]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// All slabs of one quad, L1-bypassing loads, all in flight, summed in slab order.
-__device__ __forceinline__ f32x4 deep_gather_quad(const float* slab0, unsigned stride, int ks) {
-    const deep_gu64* s0 = (const deep_gu64*)(unsigned long long)slab0;
-    unsigned long long t0[8], t1[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const size_t o = (size_t)(k < ks ? k : 0) * (stride / 2);
-        t0[k] = __hip_atomic_load(s0 + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t1[k] = __hip_atomic_load(s0 + o + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    f32x4 v = {__uint_as_float((unsigned)t0[0]), __uint_as_float((unsigned)(t0[0] >> 32)), __uint_as_float((unsigned)t1[0]), __uint_as_float((unsigned)(t1[0] >> 32))};
-#pragma unroll
-    for (int k = 1; k < 8; ++k)
-        if (k < ks) {
-            v[0] += __uint_as_float((unsigned)t0[k]);
-            v[1] += __uint_as_float((unsigned)(t0[k] >> 32));
-            v[2] += __uint_as_float((unsigned)t1[k]);
-            v[3] += __uint_as_float((unsigned)(t1[k] >> 32));
-        }
-    return v;
-}
-// After every thread of the workgroup has parked its quads: drain, take the tile's ticket; true in the workgroup that arrived last.
-// `scratch`: LDS, [0] = flag, statistics slots from +4 (zeroed here for the last arriver).
-__device__ __forceinline__ bool deep_fin_arrive(const DeepFin& f, int tile, int arrivals, float* scratch, int tid) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains its write-through stores
-    __syncthreads();
-    int* flag = reinterpret_cast<int*>(scratch);
-    if (tid == 0) {
-        const bool last = __hip_atomic_fetch_add(f.tickets + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == arrivals - 1;
-        if (last) __hip_atomic_store(f.tickets + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // self-cleaning for the next launch
-        *flag = last ? 1 : 0;
-    }
-    double* st = reinterpret_cast<double*>(scratch + 4);
-    for (int e = tid; e < f.nstat * 96 * 2; e += DEEP_NTH) st[e] = 0.0;
-    __syncthreads();
-    return *flag != 0;
-}
+// `scratch` (LDS): [0] = the launch's epoch, statistics slots from +4 (zeroed by the completing workgroup).
 // (consumer `t` of the tensor: its group size / channel offset BY VALUE -- a run-time index into a stat[] array inside a local struct
 // would put the struct in scratch memory)
 __device__ __forceinline__ void deep_stat_one(const StatOut so, int t, const SegInfo seg, float* scratch, int tok, int n, const f32x4& v) {
@@ -311,9 +269,9 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_conv(const DeepArgs a) {
     const int rgb = slot >> a.ks_shift;
     const int rg = rgb & (a.nrg - 1);
     const int b = rgb >> (a.nrg - 1);
-    // tagged completion (DeepFin::tagged): this workgroup's entry ticket -> the launch's epoch; requested first of all, read much later
+    // in-launch completion (DeepFin): this workgroup's entry ticket -> the launch's epoch; requested first of all, read much later
     // (NT == 1 tiles only: the 48-column tiles have no registers to spare -- launch_deep_conv rejects the combination)
-    const bool tg = NT == 1 && a.fin.out != nullptr && a.fin.tagged != 0;
+    const bool tg = NT == 1 && a.fin.out != nullptr;
     unsigned long long early = 0;
     if (tg && tid == 0) early = __hip_atomic_fetch_add(a.fin.ecnt + ((b * a.nrg + rg) * a.tiles_n + j), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // geometry: output level and the level of the tapped source
@@ -467,15 +425,9 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_conv(const DeepArgs a) {
             const int p = tk >= b2s ? 2 : (tk >= b1s ? 1 : 0);
             if (p != cur_p) {                                  // (rows ascend: at most three times, once for most threads)
                 cur_p = p;
-                double sx, sy;
-                if (a.whole) {
-                    sx = (sdp[(0 * DEEP_MAX_NG + gi) * 2] + sdp[(1 * DEEP_MAX_NG + gi) * 2]) + sdp[(2 * DEEP_MAX_NG + gi) * 2];
-                    sy = (sdp[(0 * DEEP_MAX_NG + gi) * 2 + 1] + sdp[(1 * DEEP_MAX_NG + gi) * 2 + 1]) + sdp[(2 * DEEP_MAX_NG + gi) * 2 + 1];
-                } else {
-                    sx = sdp[(p * DEEP_MAX_NG + gi) * 2];
-                    sy = sdp[(p * DEEP_MAX_NG + gi) * 2 + 1];
-                }
-                const double inv_n = a.whole ? a.inv_n[3] : a.inv_n[p];
+                const double sx = sdp[(p * DEEP_MAX_NG + gi) * 2];
+                const double sy = sdp[(p * DEEP_MAX_NG + gi) * 2 + 1];
+                const double inv_n = a.inv_n[p];
                 const double mean = sx * inv_n;
                 double var = sy * inv_n - mean * mean;
                 var = var < 0.0 ? 0.0 : var;
@@ -669,7 +621,6 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_conv(const DeepArgs a) {
     }
     __syncthreads();
     float* const outp = a.out + (size_t)s * a.out_slab_stride;
-    const bool fin = a.fin.out != nullptr && !tg;
     float* const fscratch = smem + a.lds_fin;
     const unsigned epoch = tg ? *reinterpret_cast<const unsigned*>(fscratch) : 0u;
     const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(a.fin.gran, 0, tg ? (int)a.fin.gran_bytes : 0, 0x00020000);
@@ -689,9 +640,7 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_conv(const DeepArgs a) {
         if (s == 0) v += (e == tid && pre_ok) ? pre : epi_operands(e);
         if (pool_r) v += (e == tid && prep_ok) ? prep : pooled_res(e);
         const size_t qoff = ((size_t)b * a.Lout + rg_tok0 + rr) * a.N + n0 + 4 * cq;
-        float* dst = outp + qoff;
-        if (fin) deep_park_quad(dst, v);
-        else mtv_store_out4(outp, qoff, v);          // (tagged completion too: consumers emitted before the plain copy was asked for read the slabs)
+        mtv_store_out4(outp, qoff, v);               // (completed tensors too: consumers emitted before the plain copy was asked for read the slabs)
         if (tg) {
             if (s) {
                 deep_put_granules(grs, (unsigned)(((size_t)(s - 1) * slice_gran + qoff) * 8), v, epoch);
@@ -703,22 +652,6 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_conv(const DeepArgs a) {
         }
     }
     if (tg && s == 0) deep_fin_flush(a.fin, fscratch, b, tid);
-    if (fin) {
-        // ---- in-launch completion: the K slice that arrives last turns the tile's slabs into the plain tensor (+ statistics)
-        float* scratch = smem + a.lds_fin;
-        if (deep_fin_arrive(a.fin, (b * a.nrg + rg) * a.tiles_n + j, a.KS, scratch, tid)) {
-            for (int e = tid; e < QUADS; e += DEEP_NTH) {
-                const int rr = e / QPR, cq = e - rr * QPR;
-                if (rr >= rg_ntok) continue;
-                const int tok = rg_tok0 + rr, n = n0 + 4 * cq;
-                const size_t off = ((size_t)b * a.Lout + tok) * a.N + n;
-                const f32x4 v = deep_gather_quad(a.out + off, a.out_slab_stride, a.KS);
-                mtv_store_out4(a.fin.out, off, v);
-                deep_fin_stat(a.fin, scratch, tok, n, v);
-            }
-            deep_fin_flush(a.fin, scratch, b, tid);
-        }
-    }
     DEEP_STAMP(7);
 }
 
@@ -846,8 +779,8 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
     const int QT = deep_usgpr(a.QT), QR = 16 * QT;            // query tiles / query rows of this workgroup
     const int q0 = qg * QR;
     const int L = a.L, C = a.C, HPW = a.HPW, NC = a.NC;
-    // tagged completion over the head groups (DeepFin::tagged): entry ticket -> the launch's epoch
-    const bool tg = a.fin.out != nullptr && a.fin.tagged != 0;
+    // in-launch completion over the head groups (DeepFin): entry ticket -> the launch's epoch
+    const bool tg = a.fin.out != nullptr;
     unsigned long long early = 0;
     if (tg && tid == 0) early = __hip_atomic_fetch_add(a.fin.ecnt + ((b * a.nqg + qg) * a.ncg + cg), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int b1 = a.r * a.r, b2 = b1 + a.t * a.r;
@@ -1143,9 +1076,7 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
             for (int k2 = 1; k2 < a.res.ks; ++k2) v += *reinterpret_cast<const f32x4*>(a.res.p + (size_t)k2 * a.res.slab_stride + ((size_t)b * L + tok) * a.res.C + n);
         }
         const size_t qoff = ((size_t)b * L + tok) * C + n;
-        float* dst = a.out + (size_t)hg * a.out_slab_stride + qoff;
-        if (a.fin.out && !tg) deep_park_quad(dst, v);
-        else mtv_store_out4(a.out + (size_t)hg * a.out_slab_stride, qoff, v);
+        mtv_store_out4(a.out + (size_t)hg * a.out_slab_stride, qoff, v);
         if (tg) {
             if (hg) {
                 deep_put_granules(grs, (unsigned)(((size_t)(hg - 1) * slice_gran + qoff) * 8), v, epoch);
@@ -1172,22 +1103,6 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
         }
     }
     if (tg && hg == 0) deep_fin_flush(a.fin, fscratch, b, tid);
-    if (a.fin.out && !tg) {
-        // ---- in-launch completion over the head groups (the K slices of the projection)
-        float* scratch = fscratch;
-        if (deep_fin_arrive(a.fin, (b * a.nqg + qg) * a.ncg + cg, a.nhg, scratch, tid)) {
-            for (int e = tid; e < QR * (NC >> 2); e += DEEP_NTH) {
-                const int rr = e / (NC >> 2), cq = e - rr * (NC >> 2);
-                const int tok = q0 + rr, n = cg * NC + 4 * cq;
-                if (tok >= L) continue;
-                const size_t off = ((size_t)b * L + tok) * C + n;
-                const f32x4 v = deep_gather_quad(a.out + off, a.out_slab_stride, a.nhg);
-                mtv_store_out4(a.fin.out, off, v);
-                deep_fin_stat(a.fin, scratch, tok, n, v);
-            }
-            deep_fin_flush(a.fin, scratch, b, tid);
-        }
-    }
     DEEP_STAMP(9);
 }
 
@@ -1998,16 +1913,15 @@ static size_t deep_layout(DeepArgs& a, DeepTile t) {
 // GroupNorm flags set; on success nrg / KS / CSm / CSs / tiles_n are filled in.  K slices: the most that keep the grid at <= 256
 // workgroups (one per CU: every CU streams its share of the weights), within what the kernel supports -- power-of-two slices of
 // 16 ... 256 channels that hold whole GroupNorm groups and do not straddle the parts of a channel concatenation.
-bool deep_configure(DeepArgs& a, DeepTile* t, int max_ks) {
+bool deep_configure(DeepArgs& a, DeepTile* t) {
     if (a.B < 1 || a.Lout < 1 || a.Lout > 128 || (a.N & 15) || (a.Cmain & 15) || (a.Cskip & 15)) return false;
     if (a.ntaps != 9 && a.ntaps != 1) return false;
-    a.nrg = (a.Lout > 64 && !(a.gn && a.whole)) ? 2 : 1;
+    a.nrg = a.Lout > 64 ? 2 : 1;
     if (!deep_tile_for(a, t)) return false;
-    if (max_ks == 1) t->NT = 1;                        // un-sliced K (plain output): column tiles are the only parallelism
     a.tiles_n = a.N / (16 * t->NT);
     const int C0m = a.main[1].p ? a.main[0].C : 0, C0s = a.skip[1].p ? a.skip[0].C : 0;
     int best = 0;
-    for (int KS = 1; KS <= max_ks; KS *= 2) {
+    for (int KS = 1; KS <= 8; KS *= 2) {
         if (a.Cmain % KS) continue;
         const int CSm = a.Cmain / KS, CSs = a.Cskip / KS;
         if (CSm < 16 || CSm > 512 || (CSm & (CSm - 1)) || (C0m && C0m % CSm)) continue;
@@ -2093,8 +2007,7 @@ hipError_t launch_deep_conv(const DeepArgs& a0, DeepTile t, hipStream_t s) {
     if (a.Cskip && (a.CSs * a.KS != a.Cskip || (a.CSs & (a.CSs - 1)) || a.CSs < 16 || a.CSs > 256)) return hipErrorInvalidValue;
     if (a.gn && ((a.gs & 3) || (a.gs & (a.gs - 1)) || a.CSm % a.gs || a.CSm / a.gs > DEEP_MAX_NG)) return hipErrorInvalidValue;
     if (a.N % (16 * t.NT) || (a.N & 3)) return hipErrorInvalidValue;
-    if (a.gn && a.whole && a.nrg != 1) return hipErrorInvalidValue;      // statistics over all planes need all planes in one workgroup
-    if (a.fin.out && a.fin.tagged && (t.NT != 1 || !a.fin.gran || !a.fin.ecnt || !a.fin.fault || a.KS < 2 || a.KS > 8)) return hipErrorInvalidValue;
+    if (a.fin.out && (t.NT != 1 || !a.fin.gran || !a.fin.ecnt || !a.fin.fault || a.KS < 2 || a.KS > 8)) return hipErrorInvalidValue;
     if (!a.zeros || !a.rowtab) return hipErrorInvalidValue;
     if ((a.pool_main && (a.up_main || a.main[1].p)) || (a.pool_res && (a.up_res || !a.res.p))) return hipErrorInvalidValue;
     if (!a.gn) { a.gamma = a.beta = a.zeros; }                           // (the kernel loads these vectors unconditionally)
@@ -2117,12 +2030,11 @@ hipError_t launch_deep_conv(const DeepArgs& a0, DeepTile t, hipStream_t s) {
     }
     a.inv_r = 1.0f / (float)a.r;
     a.inv_rs = 0.f;
-    {   // reciprocal element counts of the GroupNorm statistics (source level): planes 0, 1, 2 and all planes together
+    {   // reciprocal element counts of the GroupNorm statistics (source level): planes 0, 1, 2
         const int rs = a.up_main ? a.r >> 1 : (a.pool_main ? a.r << 1 : a.r), ts = a.up_main ? a.t >> 1 : (a.pool_main ? a.t << 1 : a.t);
         const double gsd = a.gn ? (double)a.gs : 1.0;
         a.inv_n[0] = 1.0 / ((double)rs * rs * gsd);
         a.inv_n[1] = a.inv_n[2] = 1.0 / ((double)ts * rs * gsd);
-        a.inv_n[3] = 1.0 / ((double)(rs * rs + 2 * ts * rs) * gsd);
     }
     const size_t smem = deep_layout(a, t);
     if (smem > 160 * 1024) return hipErrorInvalidValue;
@@ -2249,6 +2161,7 @@ hipError_t launch_deep_attn(const DeepAttnArgs& a0, hipStream_t s) {
     }
     const size_t smem = deep_attn_smem(a, d);
     if (smem > 160 * 1024 || !(a.res.ks >= 1 && a.res.ks <= 8)) return hipErrorInvalidValue;
+    if (a.fin.out && (!a.fin.gran || !a.fin.ecnt || !a.fin.fault || a.nhg < 2 || a.nhg > 8)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(a.ncg * a.nslots));
     if (d == 16) hipLaunchKernelGGL((k_deep_attn<16>), grid, dim3(DEEP_NTH), smem, s, a);
     else if (d == 32) hipLaunchKernelGGL((k_deep_attn<32>), grid, dim3(DEEP_NTH), smem, s, a);

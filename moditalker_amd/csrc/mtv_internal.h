@@ -289,20 +289,16 @@ struct DeepSrc {
 };
 
 // Optional in-launch completion of a deep tensor (a consumer outside the deep region -- k_conv, k_pool_down, k_attention, the
-// attention blocks' qkv -- wants ONE plain tensor and, for GroupNorm, its statistics): every K slice parks its partial tile with
-// write-through 8-byte stores and takes a ticket; the slice that draws the last one re-reads all slabs (slab order), writes the
-// plain tile and adds the statistics -- conv.hip's split-K completion (cdna_hip_programming.md G16: 8-byte agent atomics both sides).
+// attention blocks' qkv -- wants ONE plain tensor and, for GroupNorm, its statistics) by data-tagged granules (MI355X_MICROARCH.md
+// hand-off price list): every workgroup of a tile takes an entry ticket (-> the launch's epoch); K slices 1 .. KS-1 write their
+// partial quads to their slabs and also as 8-byte {value, epoch} granules; slice 0 polls them, adds them in slice order to its own
+// tile and writes the plain tensor + statistics.  No drain, no ticket wait, no re-read of the slabs.
 struct DeepFin {
-    float* out;              // plain [B][L][N] (nullptr: slabs only)
-    int* tickets;            // one per output tile (zero between launches: the last slice resets its own)
+    float* out;              // plain [B][L][N] (nullptr: slabs only, nothing below is read)
     StatOut stat[2];
     int nstat;
     unsigned stat_cstride;
     SegInfo seg;             // plane boundaries of the output level
-    // ---- round 5: completion by data-tagged granules instead of drain + ticket + re-read (MI355X_MICROARCH.md hand-off price list):
-    // every workgroup of a tile takes an entry ticket (-> the launch's epoch); K slices 1 .. KS-1 also write their partial quads as
-    // 8-byte {value, epoch} granules; slice 0 polls them, adds them in slice order to its own tile and writes the plain tensor + statistics
-    int tagged;              // 1: this form (tickets / parked slabs unused)
     float* gran;             // [slices - 1][B][L][N] granules (8 bytes each)
     unsigned gran_bytes;
     unsigned long long* ecnt;   // [tiles] monotonic entry-ticket counters (never reset)
@@ -333,7 +329,7 @@ struct DeepArgs {
     const float* film;       // per clip: scale at [c], shift at [Cmain + c]; nullptr = none
     int film_stride;
     int gs;                  // channels per group
-    int gn, whole, act;      // gn: normalise; whole: statistics over all planes (AttentionBlock1D); act: SiLU
+    int gn, act;             // gn: normalise (statistics per plane); act: SiLU
     const int* rowtab;       // device copy of deep_rowtab(): [nrg][(ntaps + 1)][16 RT] LDS offsets (floats)
     const float* zeros;      // >= 2 Cmain zero floats: stands in for absent GroupNorm / FiLM vectors (launch_deep_conv)
     float* out;              // slab 0 of the output [KS][B][Lout][N]
@@ -351,7 +347,7 @@ struct DeepArgs {
     float inv_nslots, inv_r, inv_rs;
     int lds_skip, lds_idx, lds_stat, lds_red;   // LDS offsets (floats): skip slice | row table | statistics scratch | reduction scratch
     int src_rows_max;        // rows of the staged main slice (largest row group) -- its zero row follows
-    double inv_n[4];         // 1 / (tokens x gs) of source plane 0, 1, 2 and of all planes together
+    double inv_n[3];         // 1 / (tokens x gs) of source plane 0, 1, 2
     unsigned long long* dbg; // -DMTV_DEEP_STAMP builds (tools/ubench/deep_bench): phase timestamps of two sampled workgroups, else unused
     DeepFin fin;
     int lds_fin;             // LDS offset (floats) of the completion scratch (flag + statistics slots)
@@ -521,7 +517,7 @@ bool deep_tile_for(const DeepArgs& a, DeepTile* t);      // (fills nothing in `a
 #include <vector>
 namespace mtv {
 std::vector<int> deep_rowtab(const DeepArgs& a, DeepTile t);   // host: the row table of a configured conv (upload it, pass it as DeepArgs::rowtab)
-bool deep_configure(DeepArgs& a, DeepTile* t, int max_ks = 8);   // picks row groups / K slices (<= max_ks) / tile; false: this conv stays on k_conv
+bool deep_configure(DeepArgs& a, DeepTile* t);   // picks row groups / K slices (<= 8) / tile; false: this conv stays on k_conv
 size_t deep_smem_bytes(const DeepArgs& a, DeepTile t);
 hipError_t launch_deep_conv(const DeepArgs& a, DeepTile t, hipStream_t s);
 hipError_t launch_deep_repack(const float* W, int ldw, float* dst, const DeepArgs& a, int NT, hipStream_t s);   // legacy [krow][ldw] -> deep layout

@@ -342,18 +342,24 @@ struct Builder {
         a.zeros = c->buf("deep.zeros", 8192);
         return a;
     }
-    // emit a configured deep conv (deep_configure() succeeded): output slabs, deep-layout weights, the op
-    Tens emit_deep(DeepArgs a, DeepTile t, const float* W, int ldw, const std::string& name, int lvl_out) {
+    // output of a deep-level op: `ks` partial slabs [clips][L][C], registered as the tap `name` (p == nullptr: the allocation failed)
+    Tens out_slabs(const std::string& name, int lvl, int C, int ks) {
         Tens out;
-        out.lvl = lvl_out;
-        out.C = a.N;
-        out.ks = a.KS;
-        out.slab = (unsigned)((size_t)deep_clips() * c->lv[lvl_out].L * a.N);
+        out.lvl = lvl;
+        out.C = C;
+        out.ks = ks;
+        out.slab = (unsigned)((size_t)deep_clips() * c->lv[lvl].L * C);
         // (8 slabs whatever this plan picked: plans of other batch sizes share the buffer and may slice differently)
         out.p = c->buf("act.deep." + name, (size_t)8 * out.slab);
-        c->taps[name] = {lvl_out, a.N};
+        if (!out.p) return out;
+        c->taps[name] = {lvl, C};
         c->bufs["tap." + name] = out.p;
         c->tap_slabs[name] = {out.ks, out.slab};
+        return out;
+    }
+    // emit a configured deep conv (deep_configure() succeeded): output slabs, deep-layout weights, the op
+    Tens emit_deep(DeepArgs a, DeepTile t, const float* W, int ldw, const std::string& name, int lvl_out) {
+        const Tens out = out_slabs(name, lvl_out, a.N, a.KS);
         a.out = out.p;
         a.out_slab_stride = out.slab;
         a.W = c->wdeep_for(W, ldw, a, t.NT);
@@ -404,21 +410,15 @@ struct Builder {
         o.lvl = x.lvl;
         o.C = x.C;
         o.p = c->act(name + ".fin", x.lvl, x.C);
-        // Default: a separate k_deep_finalize pass (4.6 us + a kernel boundary).  MTV_DEEP_INLAUNCH=1: completion inside the
-        // producing kernel instead (its last-arriving K slice re-reads the slabs and writes the plain tensor + statistics; consumers
-        // emitted so far keep reading the slabs) -- parity-green, and measured no faster: the store -> drain -> ticket -> re-read
-        // chain adds 4-4.5 us to the producing launch (conv3 at 32 tokens 8.3 -> 10.1 us, at 128 tokens 15.1 -> 17.1, the
-        // attention block 10.6 -> 14.8), the same three dependent round trips as k_conv's split-K completion.
-        // Round 5 default: completion inside the producing kernel by data-tagged granules (DeepFin::tagged: no drain, no ticket wait -- K slice 0
-        // polls the other slices' partial tiles; profiles/r05_tagged_fin_ab.txt).  MTV_DEEP_FIN_PASS=1 / MTV_DEEP_OPT_FIN_PASS: round 4's pass.
-        const bool ticket_inlaunch = deep_opt(MTV_DEEP_OPT_INLAUNCH, "MTV_DEEP_INLAUNCH", false);
-        const bool tagged_inlaunch = !ticket_inlaunch && !deep_opt(MTV_DEEP_OPT_FIN_PASS, "MTV_DEEP_FIN_PASS", false);
+        // Default: completion inside the producing kernel by data-tagged granules (DeepFin: no drain, no ticket wait -- K slice 0 polls the
+        // other slices' partial tiles; consumers emitted so far keep reading the slabs; profiles/r05_tagged_fin_ab.txt).  Where its
+        // conditions do not hold, or under MTV_DEEP_FIN_PASS=1 / MTV_DEEP_OPT_FIN_PASS: a separate k_deep_finalize pass (round 4).
         DeepFin* fn = nullptr;
         std::shared_ptr<void> owner;
         long ntile = 0, nwg = 0;
         int nslices = 0, lastN = 0;
         bool tile_ok = true;
-        if (ticket_inlaunch || tagged_inlaunch) {
+        if (!deep_opt(MTV_DEEP_OPT_FIN_PASS, "MTV_DEEP_FIN_PASS", false)) {
             auto dp = deep_producer.find(x.p);
             auto ap = attn_producer.find(x.p);
             if (dp != deep_producer.end()) {
@@ -430,26 +430,20 @@ struct Builder {
             }
             // (the polling slice waits for workgroups of the same launch: all of them must be resident together)
             // -> grid <= the CUs this context may count on (mtv_ctx::resident_cus); otherwise the finalize pass
-            if (fn && tagged_inlaunch && (!tile_ok || nwg > std::min(256, c->resident_cus) || nslices < 2 || nslices > 8)) fn = nullptr;
+            if (fn && (!tile_ok || nwg > std::min(256, c->resident_cus) || nslices < 2 || nslices > 8)) fn = nullptr;
         }
         if (fn) {
             fn->out = o.p;
             fn->nstat = 0;
             fn->stat_cstride = (unsigned)c->stats_copy_doubles;
             fn->seg = c->lv[x.lvl].seg();
-            if (tagged_inlaunch) {
-                const size_t gf = (size_t)(nslices - 1) * B * c->lv[x.lvl].L * lastN * 2;        // 8-byte granules
-                const std::string okey = name + ".B" + std::to_string(B) + ".S" + std::to_string(nslices);
-                fn->tagged = 1;
-                fn->gran = c->buf("deep.fin.gran." + okey, gf);                                  // (per op: tags are only unique per counter)
-                fn->gran_bytes = (unsigned)(gf * 4);
-                fn->ecnt = reinterpret_cast<unsigned long long*>(c->buf("deep.fin.ecnt." + okey, (size_t)ntile * 2));
-                fn->fault = c->fault_d;
-                if (!fn->gran || !fn->ecnt || !fn->fault) { err = "granule scratch allocation failed at " + name; return Tens{}; }
-            } else {
-                fn->tickets = reinterpret_cast<int*>(c->buf("deep.tickets." + name + ".B" + std::to_string(B), (size_t)ntile));
-                if (!fn->tickets) { err = "ticket allocation failed at " + name; return Tens{}; }
-            }
+            const size_t gf = (size_t)(nslices - 1) * B * c->lv[x.lvl].L * lastN * 2;        // 8-byte granules
+            const std::string okey = name + ".B" + std::to_string(B) + ".S" + std::to_string(nslices);
+            fn->gran = c->buf("deep.fin.gran." + okey, gf);                                  // (per op: tags are only unique per counter)
+            fn->gran_bytes = (unsigned)(gf * 4);
+            fn->ecnt = reinterpret_cast<unsigned long long*>(c->buf("deep.fin.ecnt." + okey, (size_t)ntile * 2));
+            fn->fault = c->fault_d;
+            if (!fn->gran || !fn->ecnt || !fn->fault) { err = "granule scratch allocation failed at " + name; return Tens{}; }
             fin_producer[o.p] = StatSink{fn->stat, &fn->nstat, owner};
             fin_cache[x.p] = o;
             return o;
@@ -740,12 +734,16 @@ struct Builder {
         for (int i = 0; i < t.nseg; ++i) t.blk_prefix[i + 1] = t.blk_prefix[i] + (t.seg_len[i] + 63) / 64;
         return t;
     }
+    // QK^T + PV of one clip: every query against all L keys (whole) or against the keys of its own plane
+    static double attn_flops(const Level& L, bool whole, int H, int d) {
+        if (whole) return 4.0 * H * (double)L.L * L.L * d;
+        double fl = 0.0;
+        for (int sg : {L.b1, L.b2 - L.b1, L.L - L.b2}) fl += 4.0 * H * (double)sg * sg * d;
+        return fl;
+    }
     void push_attention(AttnArgs t, const std::string& nm, const Level& L, int C, int d, bool whole) {
-        const int H = t.H;
-        if (c->accounting)
-            for (int i = 0; i < t.nseg; ++i) c->work.flops_attn_core += 4.0 * H * (double)t.seg_len[i] * t.seg_len[i] * d;
-        double aflops = 0.0;
-        for (int i = 0; i < t.nseg; ++i) aflops += 4.0 * B * H * (double)t.seg_len[i] * t.seg_len[i] * d;
+        const double aflops1 = attn_flops(L, whole, t.H, d);
+        if (c->accounting) c->work.flops_attn_core += aflops1;
         char tag[64];
         snprintf(tag, sizeof tag, "[L%d d%d %s]", L.L, d, whole ? "1d" : "2d");      // (which core runs is decided at launch: launch_attention)
         static const bool att_stamps = getenv("MTV_STAMPS") != nullptr;       // diagnostic build only (mtv_debug_stamps)
@@ -753,7 +751,7 @@ struct Builder {
             t.dbg = reinterpret_cast<unsigned long long*>(c->buf("dbg.attn." + nm + "." + std::to_string(mode) + "." + std::to_string(B), 128));
             plan->attn_dbg.emplace_back("attn:" + nm + tag, t.dbg);
         }
-        push("attn:" + nm + tag, [t](hipStream_t s) { return launch_attention(t, s); }, aflops, 4.0 * B * L.L * 4.0 * C);
+        push("attn:" + nm + tag, [t](hipStream_t s) { return launch_attention(t, s); }, B * aflops1, 4.0 * B * L.L * 4.0 * C);
     }
 
     Tens attention(const Tens& x0, const std::string& P, bool whole, const std::string& nm) {
@@ -765,49 +763,38 @@ struct Builder {
         if (!(d == 4 || d == 8 || d == 16 || d == 32 || d == 48 || d == 64 || d == 128)) { err = "head dim unsupported at " + P; return Tens{}; }
         float* gw = gnvec(P + "norm.weight", C);
         float* gb = gnvec(P + "norm.bias", C);
-        const int ldq = pad64(3 * C);
-        float* Wq = c->buf("w." + P + "qkv.weight", (size_t)C * ldq);
-        wconv(P + "qkv.weight", 3 * C, C, 1, 1, true, Wq, ldq);
-        float* Wq_nk = c->buf("wnk." + P + "qkv.weight", (size_t)3 * C * C);      // the same weights as stored, [3C][C]: k_deep_block's operand
-        c->slots[c->slot_index[P + "qkv.weight"]].dst2 = Wq_nk;
-        float* Wq_pk = (C & 15) ? nullptr : c->buf("wpk." + P + "qkv.weight", (size_t)3 * C * C);      // ... and lane-linear: k_conv_pw's operand
-        c->slots[c->slot_index[P + "qkv.weight"]].dst3 = Wq_pk;
+        // a 1x1 conv's weights [N][C]: as k_conv reads them | as stored (k_deep_block's operand) | lane-linear (k_conv_pw's and k_deep_attn's; made at weight load)
+        struct W3 { float *w, *nk, *pk; int ld; };
+        auto weights = [&](const std::string& key, int N) {
+            W3 w{};
+            w.ld = pad64(N);
+            w.w = c->buf("w." + key, (size_t)C * w.ld);
+            wconv(key, N, C, 1, 1, true, w.w, w.ld);
+            w.nk = c->buf("wnk." + key, (size_t)N * C);
+            w.pk = (C & 15) ? nullptr : c->buf("wpk." + key, (size_t)N * C);
+            c->slots[c->slot_index[key]].dst2 = w.nk;
+            c->slots[c->slot_index[key]].dst3 = w.pk;
+            return w;
+        };
+        const W3 wq = weights(P + "qkv.weight", 3 * C);
         float* bq = c->wcopy(P + "qkv.bias", {3 * C});
-        const int ldp = pad64(C);
-        float* Wp = c->buf("w." + P + "proj_out.weight", (size_t)C * ldp);
-        wconv(P + "proj_out.weight", C, C, 1, 1, true, Wp, ldp);
-        float* Wp_nk = c->buf("wnk." + P + "proj_out.weight", (size_t)C * C);
-        c->slots[c->slot_index[P + "proj_out.weight"]].dst2 = Wp_nk;
-        float* Wp_pk = (C & 15) ? nullptr : c->buf("wpk." + P + "proj_out.weight", (size_t)C * C);
-        c->slots[c->slot_index[P + "proj_out.weight"]].dst3 = Wp_pk;
+        const W3 wp = weights(P + "proj_out.weight", C);
         float* bp = c->wcopy(P + "proj_out.bias", {C});
+        const float scale = 1.0f / std::sqrt(std::sqrt((float)d));
+        const double aflops1 = attn_flops(L, whole, H, d), aflops = B * aflops1;      // per clip | per launch
 
-        // ---- deep level (deep.hip): attention core + proj_out in ONE launch (k_deep_attn; the head groups are the K slices of the
-        // projection, one output slab each).  It reads every channel of a head, so qkv must be one plain tensor: by default the
-        // block's input is summed up once (k_deep_finalize, which also leaves the GroupNorm statistics) and qkv stays on k_conv
-        // -- a K-sliced qkv conv (MTV_DEEP_QKV=1) stages ALL tokens of its channel slice per column tile and then needs its own
-        // finalize pass: measured slower at both deep levels.
-        DeepAttnArgs da{};
-        da.B = B; da.L = L.L; da.C = C; da.H = H; da.r = L.r; da.t = L.t; da.whole = whole ? 1 : 0;
-        da.scale = 1.0f / std::sqrt(std::sqrt((float)d));
-        da.Wp = Wp; da.ldw = ldp; da.bias = bp;
-        da.Wpk = Wp_pk;                                         // lane-linear copy (made at weight load): the proj B fragments go straight into registers
-        da.form = g_deep_attn_form > 0 ? g_deep_attn_form : 0;
         const bool fuse_env = !deep_opt(MTV_DEEP_OPT_NO_FUSED_ATTN, "MTV_DEEP_NO_ATTN", false);
-        const bool deep_qkv_env = deep_opt(MTV_DEEP_OPT_SLICED_QKV, "MTV_DEEP_QKV", false);
         // ---- the whole block in ONE launch (block.hip, k_deep_block): a cluster of workgroups per (clip, head) reads the input's slabs,
         // computes its GroupNorm statistics, the head's q | k | v (K-sliced inside the cluster, two in-launch hand-offs), the attention and
         // the head's share of proj_out -> output slab `head`.  No finalize pass, no statistics site, no plain qkv tensor.
-        // (the dataflow variants of round 4 describe the three-launch form: any of them selects it)
-        const bool block_env = !deep_opt(MTV_DEEP_OPT_NO_BLOCK, "MTV_DEEP_NO_BLOCK", false) && fuse_env && !deep_qkv_env &&
-                               !deep_opt(MTV_DEEP_OPT_UNSLICED_QKV, "MTV_DEEP_QKV1", false) && !deep_opt(MTV_DEEP_OPT_INLAUNCH, "MTV_DEEP_INLAUNCH", false);
+        const bool block_env = !deep_opt(MTV_DEEP_OPT_NO_BLOCK, "MTV_DEEP_NO_BLOCK", false) && fuse_env;
         if (deep_on(lvl) && block_env) {
             DeepBlockArgs ba{};
             ba.x = dsrc(x0);
             ba.B = B; ba.L = L.L; ba.C = C; ba.H = H; ba.r = L.r; ba.t = L.t; ba.whole = whole ? 1 : 0;
-            ba.scale = 1.0f / std::sqrt(std::sqrt((float)d));
+            ba.scale = scale;
             ba.gamma = gw; ba.beta = gb; ba.gs = C / 32;
-            ba.Wq = Wq_nk; ba.bq = bq; ba.Wp = Wp_nk; ba.bp = bp;
+            ba.Wq = wq.nk; ba.bq = bq; ba.Wp = wp.nk; ba.bp = bp;
             static const int force_cl = []() { const char* e = getenv("MTV_BLOCK_CL"); return e ? atoi(e) : 0; }();
             // Where it pays (profiles/r05_deep_block.txt: the block in one launch against fin + qkv + k_deep_attn of round 4, same graph
             // chains): 32 tokens 15.7 us against 21.1, [128 x 256] 21.2 against 26.8 -- but [128 x 512] 33 against 27.5: there the K slices'
@@ -818,10 +805,7 @@ struct Builder {
             static const int force_rq = []() { const char* e = getenv("MTV_BLOCK_RQ"); return e ? atoi(e) : 0; }();
             const int max_wgs = std::min(128, c->resident_cus / 2);        // all workgroups of the launch resident together, on half of what the launch may use
             if (pays && (deep_block_configure(ba, force_cl, force_rq, max_wgs) || ((force_cl || force_rq) && deep_block_configure(ba, 0, 0, max_wgs)))) {
-                Tens out;
-                out.lvl = lvl; out.C = C; out.ks = H;
-                out.slab = (unsigned)((size_t)deep_clips() * L.L * C);
-                out.p = c->buf("act.deep." + nm + ".out", (size_t)8 * out.slab);
+                const Tens out = out_slabs(nm + ".out", lvl, C, H);
                 // Scratch and counters belong to THIS op (the same op of the context's other plans -- forward / step parities -- shares them:
                 // launches are serial).  Never shared between ops: a granule is valid when its tag equals the reader's epoch, and two ops
                 // count their epochs separately -- in a shared buffer op B would accept what op A wrote at the same count.
@@ -836,17 +820,8 @@ struct Builder {
                 ba.out = out.p;
                 ba.out_slab_stride = out.slab;
                 if (!out.p || !ba.part || !ba.qkv || !ba.cnt || !ba.fault || (ba.RQ > 1 && !ba.stg)) { err = "deep block allocation failed at " + nm; return Tens{}; }
-                c->taps[nm + ".out"] = {lvl, C};
-                c->bufs["tap." + nm + ".out"] = out.p;
-                c->tap_slabs[nm + ".out"] = {out.ks, out.slab};
-                double aflops = 0.0;
-                {
-                    const int segs[3] = {L.b1, L.b2 - L.b1, L.L - L.b2};
-                    if (whole) aflops = 4.0 * B * H * (double)L.L * L.L * d;
-                    else for (int sg : segs) aflops += 4.0 * B * H * (double)sg * sg * d;
-                }
                 if (c->accounting) {
-                    c->work.flops_attn_core += aflops / B;
+                    c->work.flops_attn_core += aflops1;
                     c->work.flops_1x1 += 2.0 * (double)L.L * C * 3.0 * C + 2.0 * (double)L.L * C * C;
                     c->work.bytes_weights_other += 4.0 * (4.0 * (double)C * C + 4.0 * C);
                 }
@@ -858,28 +833,34 @@ struct Builder {
                 return out;
             }
         }
+        // ---- three launches: the block's input summed up once (materialize: which also leaves the GroupNorm statistics), qkv on k_conv, then
+        // attention core + proj_out in ONE launch (deep.hip, k_deep_attn: it reads every channel of a head, so qkv must be one plain tensor; the
+        // head groups are the K slices of the projection, one output slab each) -- or, where that form is not taken, k_attention + a proj_out conv
+        DeepAttnArgs da{};
+        da.B = B; da.L = L.L; da.C = C; da.H = H; da.r = L.r; da.t = L.t; da.whole = whole ? 1 : 0;
+        da.scale = scale;
+        da.Wp = wp.w; da.ldw = wp.ld; da.bias = bp;
+        da.Wpk = wp.pk;                                         // (the proj B fragments go straight into registers)
+        da.form = g_deep_attn_form > 0 ? g_deep_attn_form : 0;
         const bool fused = deep_on(lvl) && fuse_env && deep_attn_configure(da);
-        auto emit_fused = [&](const float* qkv_plain, const Tens& xres) -> Tens {
-            Tens out;
-            out.lvl = lvl; out.C = C; out.ks = da.nhg;
-            out.slab = (unsigned)((size_t)deep_clips() * L.L * C);
-            out.p = c->buf("act.deep." + nm + ".out", (size_t)8 * out.slab);
+        const Tens x = materialize(x0, nm + ".in");       // k_conv reads a plain tensor and the statistics its producer left
+        double* site = c->new_site();
+        add_stats({x}, lvl, site);
+        float* qkv = c->act(nm + ".qkv", lvl, 3 * C);
+        ConvArgs a{};
+        a.ntaps = 1; a.Lout = L.L; a.Lsrc = L.L; a.N = 3 * C; a.W = wq.w; a.Wpk = wq.pk; a.ldw = wq.ld; a.bias = bq; a.out = qkv;
+        a.nmain = 1; a.src[0] = x.p; a.C[0] = C; a.Cmain = C; a.seg_src = L.seg();
+        a.gn = GnIn{site, gw, gb, nullptr, 0, C / 32, whole ? 1 : 0, 0, (unsigned)c->stats_copy_doubles};
+        add_conv(a, nm + ".qkv", lvl);
+        if (fused) {
+            const Tens out = out_slabs(nm + ".out", lvl, C, da.nhg);
             if (!out.p) { err = "deep attention allocation failed at " + nm; return Tens{}; }
-            c->taps[nm + ".out"] = {lvl, C};
-            c->bufs["tap." + nm + ".out"] = out.p;
-            c->tap_slabs[nm + ".out"] = {out.ks, out.slab};
-            da.qkv = qkv_plain;
-            da.res = dsrc(xres);
+            da.qkv = qkv;
+            da.res = dsrc(x);
             da.out = out.p;
             da.out_slab_stride = out.slab;
-            double aflops = 0.0;
-            {
-                const int segs[3] = {L.b1, L.b2 - L.b1, L.L - L.b2};
-                if (whole) aflops = 4.0 * B * H * (double)L.L * L.L * d;
-                else for (int sg : segs) aflops += 4.0 * B * H * (double)sg * sg * d;
-            }
             if (c->accounting) {
-                c->work.flops_attn_core += aflops / B;
+                c->work.flops_attn_core += aflops1;
                 c->work.flops_1x1 += 2.0 * (double)L.L * C * C;
                 c->work.bytes_weights_other += 4.0 * (double)C * C + 4.0 * C;
             }
@@ -891,58 +872,7 @@ struct Builder {
                  4.0 * B * L.L * (3.0 * C + 2.0 * C) + 4.0 * (double)C * C);
             if (out.ks > 1) attn_producer[out.p] = aop;
             return out;
-        };
-        if (deep_on(lvl) && deep_qkv_env) {
-            DeepArgs dq = deep_args(lvl, 1, 3 * C, bq);
-            dq.Cmain = C;
-            dq.main[0] = dsrc(x0);
-            dq.gn = 1; dq.whole = whole ? 1 : 0; dq.act = 0; dq.gs = C / 32; dq.gamma = gw; dq.beta = gb;
-            DeepArgs dp = deep_args(lvl, 1, C, bp);
-            dp.Cmain = C;
-            dp.main[0] = DeepSrc{dp.zeros, 0, 1, C};                       // (placeholder for the attention output)
-            dp.res = dsrc(x0);
-            DeepTile tq{}, tp{};
-            if (deep_configure(dq, &tq) && (fused || deep_configure(dp, &tp))) {
-                const Tens qkvd = emit_deep(dq, tq, Wq, ldq, nm + ".qkv", lvl);
-                if (!err.empty()) return Tens{};
-                const Tens qkvp = materialize(qkvd, nm + ".qkv");
-                if (fused) return emit_fused(qkvp.p, x0);
-                float* attd = c->act(nm + ".att", lvl, C);
-                AttnArgs t = attn_args(qkvp.p, attd, L, C, H, d, whole);
-                push_attention(t, nm, L, C, d, whole);
-                Tens ad;
-                ad.lvl = lvl; ad.C = C; ad.p = attd;
-                dp.main[0] = dsrc(ad);
-                return emit_deep(dp, tp, Wp, ldp, nm + ".out", lvl);
-            }
         }
-        const Tens x = materialize(x0, nm + ".in");       // k_conv reads a plain tensor and the statistics its producer left
-        if (fused) {
-            // qkv from the plain input with the whole K per workgroup (no slices: the output is one plain tensor, which is what
-            // the attention needs), GroupNorm statistics computed in the kernel -- where all channels of a row group fit in LDS
-            // (32 tokens; 128 tokens per plane group, not with whole-L statistics)
-            // (off by default: measured 9.5 us against k_conv's 7.9 at 32 tokens -- 96 workgroups, each staging the whole input)
-            const bool ks1_env = deep_opt(MTV_DEEP_OPT_UNSLICED_QKV, "MTV_DEEP_QKV1", false);
-            DeepArgs dq = deep_args(lvl, 1, 3 * C, bq);
-            dq.Cmain = C;
-            dq.main[0] = dsrc(x);
-            dq.gn = 1; dq.whole = whole ? 1 : 0; dq.act = 0; dq.gs = C / 32; dq.gamma = gw; dq.beta = gb;
-            DeepTile tq{};
-            if (ks1_env && deep_configure(dq, &tq, 1)) {
-                const Tens qkvd = emit_deep(dq, tq, Wq, ldq, nm + ".qkv", lvl);
-                if (!err.empty()) return Tens{};
-                return emit_fused(qkvd.p, x);
-            }
-        }
-        double* site = c->new_site();
-        add_stats({x}, lvl, site);
-        float* qkv = c->act(nm + ".qkv", lvl, 3 * C);
-        ConvArgs a{};
-        a.ntaps = 1; a.Lout = L.L; a.Lsrc = L.L; a.N = 3 * C; a.W = Wq; a.Wpk = Wq_pk; a.ldw = ldq; a.bias = bq; a.out = qkv;
-        a.nmain = 1; a.src[0] = x.p; a.C[0] = C; a.Cmain = C; a.seg_src = L.seg();
-        a.gn = GnIn{site, gw, gb, nullptr, 0, C / 32, whole ? 1 : 0, 0, (unsigned)c->stats_copy_doubles};
-        add_conv(a, nm + ".qkv", lvl);
-        if (fused) return emit_fused(qkv, x);
 
         float* att = c->act(nm + ".att", lvl, C);
         push_attention(attn_args(qkv, att, L, C, H, d, whole), nm, L, C, d, whole);
@@ -950,7 +880,7 @@ struct Builder {
         Tens out;
         out.lvl = lvl; out.C = C; out.p = c->act(nm + ".out", lvl, C);
         ConvArgs p{};
-        p.ntaps = 1; p.Lout = L.L; p.Lsrc = L.L; p.Lskip = L.L; p.N = C; p.W = Wp; p.Wpk = Wp_pk; p.ldw = ldp; p.bias = bp; p.out = out.p;
+        p.ntaps = 1; p.Lout = L.L; p.Lsrc = L.L; p.Lskip = L.L; p.N = C; p.W = wp.w; p.Wpk = wp.pk; p.ldw = wp.ld; p.bias = bp; p.out = out.p;
         p.nmain = 1; p.src[0] = att; p.C[0] = C; p.Cmain = C; p.seg_src = L.seg();
         p.res = x.p;
         add_conv(p, nm + ".proj", lvl);
@@ -2209,7 +2139,8 @@ int mtv_debug_deep(int mode) {
 }
 
 int mtv_debug_deep_options(int mask) {
-    if (mask < -1 || mask > 127) return fail(MTV_ERR_INVALID, "mask must be -1 (environment / defaults) or a combination of MTV_DEEP_OPT_*");
+    if (mask < -1 || mask > 127 || (mask >= 0 && (mask & 7)))      // (bits 1, 2, 4: retired variants)
+        return fail(MTV_ERR_INVALID, "mask must be -1 (environment / defaults) or a combination of MTV_DEEP_OPT_*");
     g_deep_opts = mask;
     return MTV_OK;
 }

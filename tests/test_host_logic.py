@@ -282,3 +282,16 @@ def test_window_staged_conv_window_covers_every_tap(R, T, levels):
     lib = _lib.load()
     assert lib.mtv_selftest_win(R, T, levels) == 0
     assert lib.mtv_selftest_win(0, 4, 2) < 0
+
+
+def test_retired_deep_option_bits_are_rejected():
+    """include/mtv_hip.h, mtv_debug_deep_options: bits 1, 2 and 4 named dataflow variants that are retired -- a mask that carries one of
+    them is an error, never silently the default plan; the surviving bits (8, 16, 32, 64) and -1 are accepted (host only)."""
+    lib = _lib.load()
+    try:
+        for mask in (1, 2, 4, 3, 81):
+            assert lib.mtv_debug_deep_options(mask) < 0 and lib.mtv_last_error(), mask
+        for mask in (8, 16, 32, 64, 80, -1):
+            assert lib.mtv_debug_deep_options(mask) == _lib.MTV_OK, mask
+    finally:
+        lib.mtv_debug_deep_options(-1)

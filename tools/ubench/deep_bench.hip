@@ -24,7 +24,7 @@ struct Case {
     const char* name;
     int r, t, up;            // output-level geometry; up: tapped source on the coarser level
     int ntaps, Cm0, Cm1, Cs0, Cs1, N;
-    int gn, whole, act, film, res, up_res;
+    int gn, act, film, res, up_res;
     int ks_in, ks_res, KS, nrg, B;
 };
 
@@ -80,7 +80,7 @@ static int run_case(const Case& c) {
     float* dW = dup(W);
     a.bias = dup(bias);
     if (Cskip) a.bias2 = dup(bias2);
-    a.gn = c.gn; a.whole = c.whole; a.act = c.act; a.gs = Cmain / 32;
+    a.gn = c.gn; a.act = c.act; a.gs = Cmain / 32;
     if (c.gn) { a.gamma = dup(gamma); a.beta = dup(beta); }
     if (c.film) { a.film = dup(film); a.film_stride = 2 * Cmain; }
     a.KS = c.KS; a.CSm = Cmain / c.KS; a.CSs = Cskip / c.KS; a.nrg = c.nrg;
@@ -111,8 +111,8 @@ static int run_case(const Case& c) {
     for (int b = 0; b < c.B; ++b) {
         const int gs = Cmain / 32;
         for (int g = 0; g < 32; ++g)
-            for (int p = 0; p < (c.whole ? 1 : 3); ++p) {
-                const int t0 = c.whole ? 0 : (p == 0 ? 0 : (p == 1 ? b1s : b2s)), t1 = c.whole ? Ls : (p == 0 ? b1s : (p == 1 ? b2s : Ls));
+            for (int p = 0; p < 3; ++p) {
+                const int t0 = p == 0 ? 0 : (p == 1 ? b1s : b2s), t1 = p == 0 ? b1s : (p == 1 ? b2s : Ls);
                 double s = 0, ss = 0;
                 for (int tok = t0; tok < t1; ++tok)
                     for (int ch = g * gs; ch < (g + 1) * gs; ++ch) { const double v = xmain(b, tok, ch); s += v; ss += v * v; }
@@ -179,34 +179,33 @@ static int run_case(const Case& c) {
 
 static int do_check() {
     const Case cases[] = {
-        // name                       r  t up taps Cm0  Cm1  Cs0  Cs1   N  gn wh act film res upr ksi ksr KS nrg B
-        {"m32 conv3 gn",              4, 2, 0, 9, 128,   0,   0,   0, 128, 1, 0, 1, 0, 0, 0, 1, 1, 8, 1, 1},
-        {"m32 conv3 gn film res ks",  4, 2, 0, 9, 128,   0,   0,   0, 128, 1, 0, 1, 1, 1, 0, 8, 4, 8, 1, 1},
-        {"m32 conv3 cat+skipconv",    4, 2, 0, 9, 128,   0, 128, 128, 128, 1, 0, 1, 1, 0, 0, 4, 1, 4, 1, 1},
-        {"m32 conv3 cat main",        4, 2, 0, 9, 128, 128,   0,   0, 128, 1, 0, 1, 0, 0, 0, 4, 1, 8, 1, 1},
-        {"m32 1x1 whole qkv",         4, 2, 0, 1, 128,   0,   0,   0, 384, 1, 1, 0, 0, 0, 0, 8, 1, 8, 1, 1},
-        {"m32 1x1 raw + res",         4, 2, 0, 1, 128,   0,   0,   0, 128, 0, 0, 0, 0, 1, 0, 1, 8, 2, 1, 1},
-        {"m128 conv3 rg2",            8, 4, 0, 9, 128,   0,   0,   0, 128, 1, 0, 1, 1, 1, 0, 4, 4, 4, 2, 1},
-        {"m128 conv3 rg1",            8, 4, 0, 9, 128,   0,   0,   0, 128, 1, 0, 1, 0, 0, 0, 2, 1, 8, 1, 1},
-        {"m128 conv3 up rg2",         8, 4, 1, 9, 128,   0,   0,   0, 128, 1, 0, 1, 0, 0, 0, 8, 1, 4, 2, 1},
-        {"m128 conv3 up_res rg2",     8, 4, 0, 9, 128,   0,   0,   0, 128, 1, 0, 1, 1, 1, 1, 4, 8, 4, 2, 1},
-        {"m128 1x1 whole rg1 NT3",    8, 4, 0, 1, 256,   0,   0,   0, 768, 1, 1, 0, 0, 0, 0, 4, 1, 8, 1, 1},
-        {"m128 1x1 2d rg2",           8, 4, 0, 1, 128,   0,   0,   0, 384, 1, 0, 0, 0, 0, 0, 4, 1, 4, 2, 1},
-        {"m128 B2 conv3 rg2",         8, 4, 0, 9, 128,   0,   0,   0, 128, 1, 0, 1, 1, 1, 0, 4, 2, 4, 2, 2},
-        {"ragged r6 t3 conv3",        6, 3, 0, 9, 128,   0,   0,   0, 128, 1, 0, 1, 0, 1, 0, 2, 2, 4, 2, 1},
-        {"ragged r3 t1 conv3 rg1",    3, 1, 0, 9, 128,   0,   0,   0, 128, 1, 0, 1, 0, 0, 0, 2, 1, 8, 1, 1},
-        {"full m32 k4608",            4, 2, 0, 9, 512,   0,   0,   0, 512, 1, 0, 1, 1, 1, 0, 8, 8, 8, 1, 1},
-        {"full m32 out conv2 k5632",  4, 2, 0, 9, 512,   0, 512, 512, 512, 1, 0, 1, 1, 0, 0, 8, 1, 8, 1, 1},
-        {"full m128 k9216 rg2",       8, 4, 0, 9, 512, 512,   0,   0, 512, 1, 0, 1, 0, 0, 0, 4, 1, 4, 2, 1},
-        {"full m128 qkv whole",       8, 4, 0, 1, 512,   0,   0,   0, 1536, 1, 1, 0, 0, 0, 0, 4, 1, 8, 1, 1},
+        // name                       r  t up taps Cm0  Cm1  Cs0  Cs1   N  gn act film res upr ksi ksr KS nrg B
+        {"m32 conv3 gn",              4, 2, 0, 9, 128,   0,   0,   0, 128, 1, 1, 0, 0, 0, 1, 1, 8, 1, 1},
+        {"m32 conv3 gn film res ks",  4, 2, 0, 9, 128,   0,   0,   0, 128, 1, 1, 1, 1, 0, 8, 4, 8, 1, 1},
+        {"m32 conv3 cat+skipconv",    4, 2, 0, 9, 128,   0, 128, 128, 128, 1, 1, 1, 0, 0, 4, 1, 4, 1, 1},
+        {"m32 conv3 cat main",        4, 2, 0, 9, 128, 128,   0,   0, 128, 1, 1, 0, 0, 0, 4, 1, 8, 1, 1},
+        {"m32 1x1 raw + res",         4, 2, 0, 1, 128,   0,   0,   0, 128, 0, 0, 0, 1, 0, 1, 8, 2, 1, 1},
+        {"m128 conv3 rg2",            8, 4, 0, 9, 128,   0,   0,   0, 128, 1, 1, 1, 1, 0, 4, 4, 4, 2, 1},
+        {"m128 conv3 rg1",            8, 4, 0, 9, 128,   0,   0,   0, 128, 1, 1, 0, 0, 0, 2, 1, 8, 1, 1},
+        {"m128 conv3 up rg2",         8, 4, 1, 9, 128,   0,   0,   0, 128, 1, 1, 0, 0, 0, 8, 1, 4, 2, 1},
+        {"m128 conv3 up_res rg2",     8, 4, 0, 9, 128,   0,   0,   0, 128, 1, 1, 1, 1, 1, 4, 8, 4, 2, 1},
+        {"m128 1x1 2d rg1 NT3",       8, 4, 0, 1, 256,   0,   0,   0, 768, 1, 0, 0, 0, 0, 4, 1, 8, 1, 1},
+        {"m128 1x1 2d rg2 NT3",       8, 4, 0, 1, 256,   0,   0,   0, 768, 1, 0, 0, 0, 0, 4, 1, 8, 2, 1},
+        {"m128 1x1 2d rg2",           8, 4, 0, 1, 128,   0,   0,   0, 384, 1, 0, 0, 0, 0, 4, 1, 4, 2, 1},
+        {"m128 B2 conv3 rg2",         8, 4, 0, 9, 128,   0,   0,   0, 128, 1, 1, 1, 1, 0, 4, 2, 4, 2, 2},
+        {"ragged r6 t3 conv3",        6, 3, 0, 9, 128,   0,   0,   0, 128, 1, 1, 0, 1, 0, 2, 2, 4, 2, 1},
+        {"ragged r3 t1 conv3 rg1",    3, 1, 0, 9, 128,   0,   0,   0, 128, 1, 1, 0, 0, 0, 2, 1, 8, 1, 1},
+        {"full m32 k4608",            4, 2, 0, 9, 512,   0,   0,   0, 512, 1, 1, 1, 1, 0, 8, 8, 8, 1, 1},
+        {"full m32 out conv2 k5632",  4, 2, 0, 9, 512,   0, 512, 512, 512, 1, 1, 1, 0, 0, 8, 1, 8, 1, 1},
+        {"full m128 k9216 rg2",       8, 4, 0, 9, 512, 512,   0,   0, 512, 1, 1, 0, 0, 0, 4, 1, 4, 2, 1},
         // ResBlock(down=True): AvgPool2d folded in (up = 2: conv1 reads the pooled, transformed finer level; upr = 2: conv2's residual is the pooled raw input)
-        {"pool m32 conv1 (in9.0.h1)",  4, 2, 2, 9, 512,   0,   0,   0, 512, 1, 0, 1, 0, 0, 0, 4, 1, 8, 1, 1},
-        {"pool m32 conv2 res ks8",     4, 2, 0, 9, 128,   0,   0,   0, 128, 1, 0, 1, 1, 1, 2, 8, 8, 8, 1, 1},
-        {"pool m32 conv2 res ks4 KS8", 4, 2, 0, 9, 128,   0,   0,   0, 128, 1, 0, 1, 1, 1, 2, 8, 4, 8, 1, 1},
-        {"pool m128 conv1 rg2 (in6.0)",8, 4, 2, 9, 256,   0,   0,   0, 256, 1, 0, 1, 0, 0, 0, 1, 1, 8, 2, 1},
-        {"pool m128 conv2 res plain",  8, 4, 0, 9, 128,   0,   0,   0, 128, 1, 0, 1, 1, 1, 2, 8, 1, 4, 2, 1},
-        {"pool m128 B2 conv1 rg2",     8, 4, 2, 9, 128,   0,   0,   0, 128, 1, 0, 1, 0, 0, 0, 2, 1, 4, 2, 2},
-        {"pool ragged r6 t3 conv1",    6, 3, 2, 9, 128,   0,   0,   0, 128, 1, 0, 1, 0, 1, 2, 2, 2, 4, 2, 1},
+        {"pool m32 conv1 (in9.0.h1)",  4, 2, 2, 9, 512,   0,   0,   0, 512, 1, 1, 0, 0, 0, 4, 1, 8, 1, 1},
+        {"pool m32 conv2 res ks8",     4, 2, 0, 9, 128,   0,   0,   0, 128, 1, 1, 1, 1, 2, 8, 8, 8, 1, 1},
+        {"pool m32 conv2 res ks4 KS8", 4, 2, 0, 9, 128,   0,   0,   0, 128, 1, 1, 1, 1, 2, 8, 4, 8, 1, 1},
+        {"pool m128 conv1 rg2 (in6.0)",8, 4, 2, 9, 256,   0,   0,   0, 256, 1, 1, 0, 0, 0, 1, 1, 8, 2, 1},
+        {"pool m128 conv2 res plain",  8, 4, 0, 9, 128,   0,   0,   0, 128, 1, 1, 1, 1, 2, 8, 1, 4, 2, 1},
+        {"pool m128 B2 conv1 rg2",     8, 4, 2, 9, 128,   0,   0,   0, 128, 1, 1, 0, 0, 0, 2, 1, 4, 2, 2},
+        {"pool ragged r6 t3 conv1",    6, 3, 2, 9, 128,   0,   0,   0, 128, 1, 1, 0, 1, 2, 2, 2, 4, 2, 1},
     };
     int bad = 0;
     for (auto& c : cases) bad += run_case(c);
