@@ -301,6 +301,51 @@ int mtv_xattn_destroy(mtv_ctx* ctx);
 int mtv_xattn_forward(mtv_ctx* ctx, const float* x, const float* context, const unsigned char* mask, float* out, int batch,
                       int n_queries, int n_keys, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The audio-to-motion stage in front of MToV: AToM's MotionDecoder and its DDIM sampler (csrc/atom.hip).
+ * Replaces MotionDecoder.forward / guided_forward (AToM/model/model.py:385-470) and the loop of
+ * GaussianDiffusion.ddim_sample (AToM/model/diffusion.py:212-250).  A separate context of the same opaque type:
+ * weights go in through mtv_num_weights / mtv_weight_info / mtv_load_weight / mtv_weights_missing with the
+ * reference's state_dict keys (e.g. "seqTransDecoder.stack.0.multihead_attn.in_proj_weight" [3 D, D]); the context
+ * lists only the keys its forward reads (the reference holds several modules it never runs).
+ * Tensors: x [B, seq_len, 204] landmarks, face [B, seq_len, 204], cond [B, 2 seq_len, cond_feature_dim], times [B]
+ * int64; all device pointers.  x_pos of the reference is accepted by the Python class and unused there as here.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mtv_atom_config {
+    int32_t nfeats;            /* 204                                                        */
+    int32_t seq_len;           /* 156 (memory has 3 seq_len + 2 keys: at most 170)           */
+    int32_t latent_dim;        /* 512; multiple of 32                                        */
+    int32_t ff_size;           /* 1024                                                       */
+    int32_t num_layers;        /* 8 FiLM decoder layers                                      */
+    int32_t num_heads;         /* 8; head dim a multiple of 4, at most 64                    */
+    int32_t cond_feature_dim;  /* 1024 (HuBERT)                                              */
+    int32_t max_batch;
+} mtv_atom_config;
+int mtv_atom_create(const mtv_atom_config* cfg, mtv_ctx** out);
+int mtv_atom_destroy(mtv_ctx* ctx);
+/* Tables the host computes exactly as the reference does: rot_tab [n_pos = 3 seq_len + 2][latent_dim / 2][cos, sin] of
+ * position * rotary.freqs (rotary_embedding_torch.py:117-132), time_freqs [latent_dim / 2] of SinusoidalPosEmb
+ * (utils.py:41-48).  Host or device pointers. */
+int mtv_atom_set_tables(mtv_ctx* ctx, const float* rot_tab, int n_pos, const float* time_freqs);
+/* One forward with every clip's condition kept (drop = 0) or replaced by the null embeddings (drop = 1):
+ * cond_drop_prob of model.py:391-399 restricted to the two values inference uses.  out [B, seq_len, 204]. */
+int mtv_atom_forward(mtv_ctx* ctx, const float* x, const float* face, const float* cond, const int64_t* times, int drop,
+                     float* out, int batch, void* stream);
+/* unc + (cond - unc) * guidance_weight (model.py:385-389): both passes as one batch of 2 B clips. */
+int mtv_atom_guided_forward(mtv_ctx* ctx, const float* x, const float* face, const float* cond, const int64_t* times,
+                            float guidance_weight, float* out, int batch, void* stream);
+/* Guidance weight of the sampler below (GaussianDiffusion.guidance_weight, diffusion.py:77,131-133); default 1. */
+int mtv_atom_set_guidance(mtv_ctx* ctx, float guidance_weight);
+/* The loop of ddim_sample for `n_steps` consecutive steps: x_start = clamp(guided_forward(x_t, t), -1, 1);
+ * pred_noise = (sqrt_recip_ac x_t - x_start) / sqrt_recipm1_ac; x <- x_start sqrt_ac_next + c pred_noise + sigma noise;
+ * the last step leaves x_start.  x_io [B, seq_len, 204] in: x_T, out: the sample; noise [n_noise, B, seq_len, 204].
+ * The timestep-invariant part of the model (condition encoders, cross-attention keys / values) runs once per call,
+ * every step is one replay of a linear hipGraph; no host synchronisation in the loop. */
+int mtv_atom_ddim_sample(mtv_ctx* ctx, float* x_io, const float* face, const float* cond, const float* noise, int n_noise,
+                         const mtv_ddim_step* steps, int n_steps, int batch, void* stream);
+/* Launches of one sampler step at this batch size (introspection for tools/atom_bench.py). */
+int mtv_atom_num_launches(mtv_ctx* ctx, int batch, int* per_step);
+
 #ifdef __cplusplus
 }
 #endif

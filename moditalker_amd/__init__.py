@@ -7,6 +7,13 @@ from .ddpm import DDPM, ddim_time_pairs, make_beta_schedule  # noqa: F401
 from .unet import DiffusionWrapper, UNetModel  # noqa: F401
 from .autoencoder import ViTAutoencoder  # noqa: F401
 from .cross_attention import CrossAttention  # noqa: F401
+from .atom import GaussianDiffusion, MotionDecoder  # noqa: F401
+
+ATOM_CONFIG = dict(  # AToM/AToM.py:57-81: the decoder and the diffusion around it (horizon 156, HuBERT features)
+    nfeats=204, seq_len=156, latent_dim=512, ff_size=1024, num_layers=8, num_heads=8, dropout=0.1, cond_feature_dim=1024,
+)
+ATOM_DIFFUSION_CONFIG = dict(schedule="cosine", n_timestep=1000, predict_epsilon=False, loss_type="l2", use_p2=False,
+                             cond_drop_prob=0.25, guidance_weight=2)
 
 BASE_AE_DDCONFIG = dict(  # MToV/configs/autoencoder/base.yaml:12-24 (embed_dim: 4)
     double_z=False, channels=384, resolution=256, timesteps=16, skip=1, in_channels=3, out_ch=3, num_res_blocks=2,

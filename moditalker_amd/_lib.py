@@ -48,6 +48,11 @@ class MtvXattnConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("query_dim", "context_dim", "heads", "dim_head", "max_batch", "max_queries", "max_keys")]
 
 
+class MtvAtomConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("nfeats", "seq_len", "latent_dim", "ff_size", "num_layers", "num_heads", "cond_feature_dim",
+                                         "max_batch")]
+
+
 class MtvDdimStep(C.Structure):
     _fields_ = [
         ("t", C.c_int32),
@@ -117,6 +122,14 @@ SYMBOLS = [
     ("mtv_xattn_create", C.c_int, [C.POINTER(MtvXattnConfig), C.POINTER(_P)]),
     ("mtv_xattn_destroy", C.c_int, [_P]),
     ("mtv_xattn_forward", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    ("mtv_atom_create", C.c_int, [C.POINTER(MtvAtomConfig), C.POINTER(_P)]),
+    ("mtv_atom_destroy", C.c_int, [_P]),
+    ("mtv_atom_set_tables", C.c_int, [_P, _P, C.c_int, _P]),
+    ("mtv_atom_forward", C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P]),
+    ("mtv_atom_guided_forward", C.c_int, [_P, _P, _P, _P, _P, C.c_float, _P, C.c_int, _P]),
+    ("mtv_atom_set_guidance", C.c_int, [_P, C.c_float]),
+    ("mtv_atom_ddim_sample", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(MtvDdimStep), C.c_int, C.c_int, _P]),
+    ("mtv_atom_num_launches", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     ("mtv_selftest_geometry", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_deep", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_block", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

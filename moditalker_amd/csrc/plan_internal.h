@@ -130,13 +130,13 @@ struct Plan {
 };
 
 
-enum CtxKind { CTX_UNET = 0, CTX_AE = 1, CTX_XATTN = 2 };
+enum CtxKind { CTX_UNET = 0, CTX_AE = 1, CTX_XATTN = 2, CTX_ATOM = 3 };
 
 struct mtv_ctx {
     mtv_config cfg{};
     int device = 0;
     int kind = CTX_UNET;                        // which C-ABI family owns this context
-    std::shared_ptr<void> ext;                  // CTX_AE: mtv_ae_config; CTX_XATTN: its weight / workspace record -- lives and dies
+    std::shared_ptr<void> ext;                  // CTX_AE: mtv_ae_config; CTX_XATTN / CTX_ATOM: its weight / workspace record -- lives and dies
                                                 // with the context (no process-global side tables, nothing to lock)
     std::vector<Level> lv;
     std::vector<Stage> inputs, outputs;

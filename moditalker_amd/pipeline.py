@@ -169,6 +169,42 @@ def reference_from_uint8(last_u8: np.ndarray, frames: int = 16) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# the stage in front: audio -> motion (AToM/inference.py:101-164)
+# ------------------------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def audio_to_motion(hubert, first_frame_kpts, diffusion, key_mean_shape, save_dir: Optional[str] = None, chunk: int = 0,
+                    noise=None) -> np.ndarray:
+    """One horizon of AToM sampling as AToM/inference.py:113-164 runs it, on moditalker_amd.GaussianDiffusion.
+      hubert            [T, cond_feature_dim] HuBERT features of the driving audio (two per video frame); rows
+                        [chunk * horizon, chunk * horizon + 2 * horizon) condition this chunk
+      first_frame_kpts  the identity's first-frame landmarks, 204 values in any shape ([68, 3], [1, 1, 204], ...)
+      key_mean_shape    the 3DMM mean landmark shape (Face3DHelper.key_mean_shape), 204 values
+    `face` is the first-frame landmarks repeated over the horizon (AToM.py:158-164, 214-220); the sampler's output is a
+    residual on them, the sum is /10 + the mean shape.  Returns [horizon, 68, 3] float32 and, with save_dir, writes
+    <save_dir>/atom_<chunk>.npy."""
+    horizon = int(diffusion.horizon)
+    dev = diffusion.betas.device
+    kp = torch.as_tensor(np.asarray(first_frame_kpts), dtype=torch.float32).reshape(1, 1, -1)
+    if kp.shape[-1] != 204:
+        raise ValueError(f"first_frame_kpts must hold 68 x 3 values; got {kp.shape[-1]}")
+    face = kp.repeat(1, horizon, 1)
+    cond = torch.as_tensor(np.asarray(hubert), dtype=torch.float32)
+    if cond.dim() != 2:
+        raise ValueError(f"hubert must be [T, feature_dim]; got {tuple(cond.shape)}")
+    cond = cond[chunk * horizon: chunk * horizon + 2 * horizon].unsqueeze(0)
+    if cond.shape[1] != 2 * horizon:
+        raise ValueError(f"chunk {chunk} needs {2 * horizon} HuBERT rows from {chunk * horizon}; the file has {int(np.asarray(hubert).shape[0])}")
+    pos = torch.zeros(1, horizon, 3)
+    out = diffusion.render_sample(None, [1, horizon, 204], face.to(dev), None, pos, None, cond.to(dev), 0, "", noise=noise)[0]
+    out = (out.reshape(horizon, 204).float() + face[0]) / 10 + torch.as_tensor(np.asarray(key_mean_shape), dtype=torch.float32).reshape(1, 204)
+    out = out.reshape(horizon, 68, 3).numpy().astype(np.float32)
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        np.save(os.path.join(save_dir, f"atom_{chunk}.npy"), out)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # the chunk loop (sample.py:305-400)
 # ------------------------------------------------------------------------------------------------------------------
 class MToVSampler:
