@@ -345,6 +345,19 @@ int mtv_atom_ddim_sample(mtv_ctx* ctx, float* x_io, const float* face, const flo
                          const mtv_ddim_step* steps, int n_steps, int batch, void* stream);
 /* Launches of one sampler step at this batch size (introspection for tools/atom_bench.py). */
 int mtv_atom_num_launches(mtv_ctx* ctx, int batch, int* per_step);
+/* The loop of GaussianDiffusion.long_ddim_sample (AToM/model/diffusion.py:252-301), the EDGE-style sampler for motion
+ * longer than one horizon: `batch` >= 2 half-overlapping windows denoised as one batch.  As mtv_atom_ddim_sample, plus
+ *   - step i runs with guidance weight weights[i] (host array of n_steps floats; the reference's ramp
+ *     np.clip(np.linspace(0, 2 w, 50), None, w), rounded to fp32, step 0 exactly 0) instead of mtv_atom_set_guidance's;
+ *   - after the update of every step that is not `last`: x[b][w] <- x[b - 1][w + seq_len / 2] for b >= 1,
+ *     w < seq_len / 2 (the values just computed); the `last` step leaves the clamped x_start unstitched, as the reference.
+ * The stitch is part of the last launch of a step: the sample lives in two buffers and steps alternate between them,
+ * so no launch reads what it writes.  seq_len must be even.  Running the first n_steps < 50 records returns x_t there
+ * (after the update and the stitch).  Errors are reported before any launch. */
+int mtv_atom_long_ddim_sample(mtv_ctx* ctx, float* x_io, const float* face, const float* cond, const float* noise, int n_noise,
+                              const mtv_ddim_step* steps, int n_steps, const float* weights, int batch, void* stream);
+/* Launches of one step of the long sampler at this batch size: the same chain as mtv_atom_num_launches reports. */
+int mtv_atom_long_num_launches(mtv_ctx* ctx, int batch, int* per_step);
 
 #ifdef __cplusplus
 }

@@ -130,6 +130,8 @@ SYMBOLS = [
     ("mtv_atom_set_guidance", C.c_int, [_P, C.c_float]),
     ("mtv_atom_ddim_sample", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(MtvDdimStep), C.c_int, C.c_int, _P]),
     ("mtv_atom_num_launches", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("mtv_atom_long_ddim_sample", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(MtvDdimStep), C.c_int, C.POINTER(C.c_float), C.c_int, _P]),
+    ("mtv_atom_long_num_launches", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     ("mtv_selftest_geometry", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_deep", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_block", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

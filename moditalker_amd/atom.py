@@ -4,8 +4,8 @@
 HuBERT features [B, 2 L, cond_feature_dim] and first-frame landmarks repeated over the horizon [B, L, 204] in, a landmark
 residual sequence [B, L, 204] out.  Both classes are parameter holders with the reference's state_dict keys and shapes (a
 reference checkpoint loads with strict=True); the arithmetic runs in libmtv_hip.so (csrc/atom.hip): `mtv_atom_forward`,
-`mtv_atom_guided_forward`, `mtv_atom_ddim_sample`.  Inference only: training, the ancestral loop and cond_drop_prob other
-than 0 or 1 raise.  No CPU fallback.
+`mtv_atom_guided_forward`, `mtv_atom_ddim_sample`, `mtv_atom_long_ddim_sample` (motion longer than one horizon:
+diffusion.py:252-301).  Inference only: training, the ancestral loop and cond_drop_prob other than 0 or 1 raise.  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -304,13 +304,7 @@ class GaussianDiffusion(nn.Module):
         model = self.model
         shape = tuple(int(s) for s in shape)
         steps, n_draws = self.step_table()
-        if noise is None:
-            noise = [torch.randn(shape, device=dev) for _ in range(1 + n_draws)]
-        if isinstance(noise, (list, tuple)):
-            noise = torch.stack([n.to(dev) for n in list(noise)[: 1 + n_draws]])
-        noise = noise.to(device=dev, dtype=torch.float32).contiguous()
-        if noise.shape[0] < 1 + n_draws or tuple(noise.shape[1:]) != shape:
-            raise ValueError(f"noise must be [{1 + n_draws},{','.join(map(str, shape))}] (x_T, then one draw per non-final step); got {tuple(noise.shape)}")
+        noise = self._noise(shape, noise, n_draws, dev)
         face, cond = face.to(dev), cond.to(dev)
         x = noise[0].clone()
         B = model.check_inputs(x, face, cond)
@@ -325,6 +319,62 @@ class GaussianDiffusion(nn.Module):
                                                 steps, len(steps), B, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtv_atom_ddim_sample")
         return x
 
+    @staticmethod
+    def _noise(shape, noise, n_draws, dev):
+        """The samplers' `noise` argument as one fp32 tensor [>= 1 + n_draws, *shape] on `dev`; ValueError for any other shape."""
+        if noise is None:
+            noise = [torch.randn(shape, device=dev) for _ in range(1 + n_draws)]
+        if isinstance(noise, (list, tuple)):
+            noise = torch.stack([n.to(dev) for n in list(noise)[: 1 + n_draws]])
+        noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+        if noise.shape[0] < 1 + n_draws or tuple(noise.shape[1:]) != shape:
+            raise ValueError(f"noise must be [{1 + n_draws},{','.join(map(str, shape))}] (x_T, then one draw per non-final step); got {tuple(noise.shape)}")
+        return noise
+
+    def long_guidance_weights(self) -> np.ndarray:
+        """diffusion.py:269: the guidance weight of each of the 50 steps of long_ddim_sample, a ramp from 0 that reaches
+        guidance_weight half way.  float32: the reference multiplies an fp32 tensor by the (fp64) scalar, which rounds it so."""
+        return np.clip(np.linspace(0, self.guidance_weight * 2, DDIM_STEPS), None, self.guidance_weight).astype(np.float32)
+
+    @torch.no_grad()
+    def long_ddim_sample(self, shape, face, x_pos, cond, noise=None, strict=None, n_steps=None, **kwargs):
+        """diffusion.py:252-301, the EDGE-style sampler for motion longer than one horizon, with the signature of ddim_sample
+        (the reference's own method predates `face` / `x_pos` and cannot be called as written).  shape [B, L, 204]: B windows that
+        overlap their neighbours by L / 2 frames are denoised as one batch; after every step but the last, the first half of
+        window b is overwritten with the second half of window b - 1, and the guidance weight ramps up over the first 25 steps
+        (long_guidance_weights).  B == 1 is ddim_sample (:262-263).  `noise` as in ddim_sample: [1 + 49, B, L, 204], x_T first.
+        `n_steps` (appended kwarg, for diagnosis and tests): run only the first n_steps < 50 steps and return x_t there, after
+        the update and the stitch."""
+        shape = tuple(int(s) for s in shape)
+        if shape[0] == 1:
+            if n_steps is not None:
+                raise ValueError("n_steps is an argument of the multi-window sampler; one window is ddim_sample")
+            return self.ddim_sample(shape, face, x_pos, cond, noise=noise, strict=strict, **kwargs)
+        if not self.clip_denoised:
+            raise NotImplementedError("clip_denoised=False is not built (every AToM configuration clamps x_start)")
+        if len(shape) != 3 or shape[1] % 2:
+            raise ValueError(f"long_ddim_sample needs an even horizon (windows overlap by half, diffusion.py:276-277); got shape {shape}")
+        dev = self.betas.device
+        model = self.model
+        steps, n_draws = self.step_table()
+        n_run = len(steps) if n_steps is None else int(n_steps)
+        if not 1 <= n_run <= len(steps):
+            raise ValueError(f"n_steps must be in [1, {len(steps)}]; got {n_steps}")
+        noise = self._noise(shape, noise, n_draws, dev)
+        face, cond = face.to(dev), cond.to(dev)
+        x = noise[0].clone()
+        B = model.check_inputs(x, face, cond)
+        weights = np.ascontiguousarray(self.long_guidance_weights())
+        ctx = model._context(dev, B)
+        ff = face.to(torch.float32).contiguous()
+        cf = cond.to(torch.float32).contiguous()
+        draws = noise[1:]
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().mtv_atom_long_ddim_sample(
+                ctx, x.data_ptr(), ff.data_ptr(), cf.data_ptr(), draws.data_ptr(), int(draws.shape[0]), steps, n_run,
+                weights.ctypes.data_as(C.POINTER(C.c_float)), B, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtv_atom_long_ddim_sample")
+        return x
+
     @torch.no_grad()
     def render_sample(self, face3d_helper, shape, kpt, front, x_pos, gt, cond, epoch, render_out, fk_out=None, name=None, sound=True,
                       mode="normal", noise=None, constraint=None, sound_folder="ood_sliced", start_point=None, render=True, filename=None,
@@ -333,7 +383,7 @@ class GaussianDiffusion(nn.Module):
         return self.ddim_sample(shape, kpt, x_pos, cond, noise=noise).detach().cpu()
 
     def _training(self, *a, **k):
-        raise NotImplementedError("moditalker_amd.GaussianDiffusion is the sampling path (ddim_sample / render_sample); training, q_sample losses "
-                                  "and the ancestral p_sample loop are not built")
+        raise NotImplementedError("moditalker_amd.GaussianDiffusion is the sampling path (ddim_sample / long_ddim_sample / render_sample); training, "
+                                  "q_sample losses and the ancestral p_sample loop are not built")
 
-    forward = loss = p_losses = p_sample = p_sample_loop = long_ddim_sample = inpaint_loop = long_inpaint_loop = conditional_sample = _training
+    forward = loss = p_losses = p_sample = p_sample_loop = inpaint_loop = long_inpaint_loop = conditional_sample = _training

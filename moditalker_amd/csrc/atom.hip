@@ -14,6 +14,9 @@
 //     its epilogue.
 //   * a step is a plain chain of launches on one stream, captured once as a linear hipGraph.  The step's scalars live in a device record that
 //     the FIRST launch of the chain (k_atom_advance, an ordinary one-thread kernel) copies from the step table: no in-launch hand-offs.
+//   * the long sampler (diffusion.py:252-301: B half-overlapping windows as one batch) is the same chain: its per-step guidance weight comes
+//     from a table k_atom_advance reads, its stitch x[b][w] <- x[b - 1][w + L / 2] is two stores of the DDIM epilogue.  The epilogue then must
+//     not write the buffer it reads, so the sample has two buffers and even / odd steps are two graphs (x_io -> x_alt, x_alt -> x_io).
 //
 // Kernels: k_tok_linear (LayerNorm + rotary prologue, exact-f32 MFMA GEMM against [N][K] weights as the checkpoint stores them, bias /
 // GELU / Mish / SiLU / FiLM / residual / guidance epilogues) and k_atom_attn (softmax attention of one head for 16 queries; any query
@@ -62,7 +65,9 @@ struct TokLinArgs {
     int ldo;
     int half_rows;                 // EPI_GUIDE: input row of the conditional half = row + half_rows
     const AtomCur* cur;
-    float* x_io;                   // EPI_GUIDE with cur->ddim: the sample, [M][N], updated in place
+    float* x_io;                   // EPI_GUIDE with cur->ddim: the sample x_t, [M][N]
+    float* x_out;                  // ... and where the updated sample goes: x_io itself (ddim_sample), the other buffer of the pair (long sampler)
+    int stitch_L;                  // long sampler: clip length L (even); 0: no stitch
 };
 
 __device__ __forceinline__ float act_apply(float y, int act) {
@@ -229,7 +234,14 @@ __global__ __launch_bounds__(256) void k_tok_linear(const TokLinArgs a) {
                     o[i] = cu.st.last ? x0
                                       : __fadd_rn(__fadd_rn(__fmul_rn(x0, cu.st.sqrt_ac_next), __fmul_rn(cu.st.c, pn)), __fmul_rn(cu.st.sigma, nz[i]));
                 }
-                *reinterpret_cast<f32x4*>(a.x_io + idx) = o;
+                // long_ddim_sample's stitch (diffusion.py:299-300) after every non-final step: x[b][w] <- x[b - 1][w + L / 2] for b >= 1, w < L / 2.
+                // The row r + L / 2 IS (b + 1, w - L / 2): the owner of a second-half row stores it twice, the owner of a first-half row of a later
+                // window stores nothing.  x_out is not x_io there, so no workgroup reads what another one writes in this launch.
+                const int half = a.stitch_L >> 1;
+                const bool stitch = a.stitch_L != 0 && !cu.st.last;
+                const int w = stitch ? r % a.stitch_L : 0;
+                if (!stitch || r < a.stitch_L || w >= half) *reinterpret_cast<f32x4*>(a.x_out + idx) = o;
+                if (stitch && w >= half && r + half < a.M) *reinterpret_cast<f32x4*>(a.x_out + idx + (size_t)half * a.N) = o;
                 return;
             }
         }
@@ -343,12 +355,14 @@ __global__ void k_atom_times(const int64_t* t, float* tv, int nb, int B) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nb) tv[i] = (float)t[i % B];
 }
-// first launch of a sampler step: the step's scalars -> the record the final epilogue reads, its timestep -> every clip, counter + 1
-__global__ void k_atom_advance(const DdimStep* steps, int* counter, AtomCur* cur, float* tv, int nb) {
+// first launch of a sampler step: the step's scalars -> the record the final epilogue reads, its timestep -> every clip, counter + 1.
+// gws (long sampler, else nullptr: the weight atom_write_cur wrote stays): the step's guidance weight from the table beside the steps.
+__global__ void k_atom_advance(const DdimStep* steps, const float* gws, int* counter, AtomCur* cur, float* tv, int nb) {
     if (blockIdx.x || threadIdx.x) return;
     const int i = *counter;
     const DdimStep st = steps[i];
     cur->st = st;
+    if (gws) cur->gw = gws[i];
     for (int b = 0; b < nb; ++b) tv[b] = (float)st.t;
     *counter = i + 1;
 }
@@ -388,17 +402,19 @@ struct AtomState {
     std::map<std::string, float*> w;            // parameter name -> device copy (the checkpoint's own layout)
     float *Wfilm, *bfilm, *Win, *bin, *rot, *tfreq;
     bool tables = false;
-    float *x_io, *X, *QKV, *ATT, *XT, *OUT;
+    float *x_io, *x_alt, *X, *QKV, *ATT, *XT, *OUT;      // x_alt: the long sampler's second sample buffer (steps alternate x_io -> x_alt -> x_io)
     float *CT, *FT, *EQKV, *EATT, *EFF, *Cmem, *Cface, *pool, *hid1, *fh, *ch, *hid_add;
     float *tv, *tsin, *th, *tvec, *ttok, *film;
     std::vector<float*> KVm, KVf;
     AtomCur* cur;
     DdimStep* steps;
+    float* gws;                                 // [steps_cap] per-step guidance weights of the long sampler, behind the step records
     int steps_cap;
     int* counter;
     float gw = 1.0f;
     AtomCur h_cur{};                            // host copies of what goes up asynchronously (they outlive the call)
     std::vector<DdimStep> h_steps;
+    std::vector<float> h_gws;
 };
 AtomState* atom_of(mtv_ctx* c) { return c && c->kind == CTX_ATOM ? static_cast<AtomState*>(c->ext.get()) : nullptr; }
 
@@ -550,12 +566,13 @@ hipError_t atom_setup(AtomState& A, int B, int mode, const float* face, const fl
 }
 
 // The launch chain of one forward / one sampler step for nb effective clips (guided: nb = 2 B, the halves meet in final_layer).
-//   x_src [B][L][204]: the landmarks (the sampler: A.x_io).  Reference behaviour kept as is:
+//   x_src [B][L][204]: the landmarks (the sampler: the sample x_t).  x_out (sampler): where the DDIM update goes -- nullptr: x_src, in
+//   place; with `stitch` (the long sampler) the other buffer of the pair.  Reference behaviour kept as is:
 //   - lip_t, nonlip_t and t are ONE tensor (model.py:441-460): every FiLM sees t0 + 2 face_hidden + cond_hidden, film3's mean of the two is that vector;
 //   - the norm_first decoder layer never runs linear1 / linear2; it ends x_tmp + affine(x_tmp, film3) -> linear3 (model.py:161-183);
 //   - norm1 + self_attn serve both streams; norm2 + self_attn the face stream, norm2 + multihead_attn on memory the lip stream;
 //     norm3 + multihead_attn again on face_memory for the sum.
-void atom_build_step(AtomState* Ap, Plan* p, int B, bool guided, bool sampler, const float* x_src) {
+void atom_build_step(AtomState* Ap, Plan* p, int B, bool guided, bool sampler, float* x_src, float* x_out = nullptr, bool stitch = false) {
     AtomState& A = *Ap;
     const int D = A.D, L = A.L, Lm = A.Lm, Lf = A.Lf, H = A.f.num_heads, d = D / H;
     const int nb = guided ? 2 * B : B, M = nb * L;
@@ -563,8 +580,8 @@ void atom_build_step(AtomState* Ap, Plan* p, int B, bool guided, bool sampler, c
     auto add_lin = [&](const std::string& name, const TokLinArgs& a) { add(name, [a](hipStream_t s) { return launch_tok_linear(a, s); }); };
     auto add_att = [&](const std::string& name, const AtomAttnArgs& t, int n) { add(name, [t, n](hipStream_t s) { return launch_atom_attn(t, n, s); }); };
     if (sampler)
-        add("advance", [Ap, nb](hipStream_t s) {
-            hipLaunchKernelGGL(k_atom_advance, dim3(1), dim3(64), 0, s, Ap->steps, Ap->counter, Ap->cur, Ap->tv, nb);
+        add("advance", [Ap, nb, stitch](hipStream_t s) {
+            hipLaunchKernelGGL(k_atom_advance, dim3(1), dim3(64), 0, s, Ap->steps, stitch ? Ap->gws : (const float*)nullptr, Ap->counter, Ap->cur, Ap->tv, nb);
             return hipGetLastError();
         });
     add("time_sin", [Ap, nb, D](hipStream_t s) {
@@ -718,19 +735,25 @@ void atom_build_step(AtomState* Ap, Plan* p, int B, bool guided, bool sampler, c
         a.epi = EPI_GUIDE;
         a.half_rows = B * L;
         a.cur = A.cur;
-        a.x_io = A.x_io;
+        a.x_io = sampler ? x_src : A.x_io;
+        a.x_out = sampler && x_out ? x_out : a.x_io;
+        a.stitch_L = stitch ? L : 0;
     }
     add_lin("final_layer", a);
 }
 
-enum { ATOM_FORWARD = 0, ATOM_GUIDED = 1, ATOM_STEP = 2 };
+// ATOM_LONG0 / ATOM_LONG1: a step of the long sampler reading x_io and writing x_alt / the reverse (even / odd steps of a call)
+enum { ATOM_FORWARD = 0, ATOM_GUIDED = 1, ATOM_STEP = 2, ATOM_LONG0 = 3, ATOM_LONG1 = 4 };
 int atom_plan(mtv_ctx* c, AtomState* A, int B, int mode, Plan** out) {
     auto it = c->plans.find({B, mode});
     if (it == c->plans.end()) {
         std::unique_ptr<Plan> p(new Plan());
         p->B = B;
         p->mode = mode;
-        atom_build_step(A, p.get(), B, mode != ATOM_FORWARD, mode == ATOM_STEP, mode == ATOM_STEP ? A->x_io : A->OUT + (size_t)A->nbmax * A->L * NFEAT);
+        if (mode == ATOM_LONG0 || mode == ATOM_LONG1)
+            atom_build_step(A, p.get(), B, true, true, mode == ATOM_LONG0 ? A->x_io : A->x_alt, mode == ATOM_LONG0 ? A->x_alt : A->x_io, true);
+        else
+            atom_build_step(A, p.get(), B, mode != ATOM_FORWARD, mode == ATOM_STEP, mode == ATOM_STEP ? A->x_io : A->OUT + (size_t)A->nbmax * A->L * NFEAT);
         it = c->plans.emplace(std::make_pair(B, mode), std::move(p)).first;
     }
     *out = it->second.get();
@@ -834,6 +857,7 @@ int mtv_atom_create(const mtv_atom_config* cfg, mtv_ctx** out) {
     BUF(A.rot, "a.rot", (size_t)Lm * D);
     BUF(A.tfreq, "a.tfreq", (size_t)D / 2);
     BUF(A.x_io, "a.x_io", (size_t)B * L * NFEAT);
+    BUF(A.x_alt, "a.x_alt", (size_t)B * L * NFEAT);
     BUF(A.X, "a.X", (size_t)nb * L * 2 * D);
     BUF(A.QKV, "a.QKV", (size_t)nb * L * 6 * D);
     BUF(A.ATT, "a.ATT", (size_t)nb * L * 2 * D);
@@ -865,11 +889,12 @@ int mtv_atom_create(const mtv_atom_config* cfg, mtv_ctx** out) {
     }
     float* rec = nullptr;
     A.steps_cap = 1024;
-    BUF(rec, "a.rec", (sizeof(AtomCur) + 64 + (size_t)A.steps_cap * sizeof(DdimStep)) / 4 + 16);
+    BUF(rec, "a.rec", (sizeof(AtomCur) + 64 + (size_t)A.steps_cap * sizeof(DdimStep)) / 4 + 16 + (size_t)A.steps_cap);
     if (!ok) return fail(MTV_ERR_HIP, "allocation failed");
     A.cur = reinterpret_cast<AtomCur*>(rec);
     A.counter = reinterpret_cast<int*>(rec + (sizeof(AtomCur) + 15) / 16 * 4);
     A.steps = reinterpret_cast<DdimStep*>(rec + (sizeof(AtomCur) + 15) / 16 * 4 + 16);
+    A.gws = reinterpret_cast<float*>(A.steps + A.steps_cap);
     c->kind = CTX_ATOM;
     c->ext = st;
     *out = c.release();
@@ -952,12 +977,10 @@ int mtv_atom_guided_forward(mtv_ctx* c, const float* x, const float* face, const
     return MTV_OK;
 }
 
-int mtv_atom_ddim_sample(mtv_ctx* c, float* x_io, const float* face, const float* cond, const float* noise, int n_noise,
-                         const mtv_ddim_step* steps, int n_steps, int batch, void* stream) {
+// the argument checks both samplers share; nothing has been launched when they fail
+static int atom_check_sample(AtomState* A, const float* x_io, const float* face, const float* cond, const float* noise, int n_noise,
+                             const mtv_ddim_step* steps, int n_steps) {
     static_assert(sizeof(DdimStep) == sizeof(mtv_ddim_step), "step layout");
-    AtomState* A = atom_of(c);
-    int rc = atom_ready(c, A, batch);
-    if (rc != MTV_OK) return rc;
     if (!x_io || !face || !cond || !steps) return fail(MTV_ERR_INVALID, "null tensor pointer");
     if (n_steps < 1 || n_steps > A->steps_cap) return fail(MTV_ERR_INVALID, "n_steps outside [1, 1024]");
     for (int i = 0; i < n_steps; ++i) {
@@ -965,6 +988,15 @@ int mtv_atom_ddim_sample(mtv_ctx* c, float* x_io, const float* face, const float
             return fail(MTV_ERR_INVALID, "step " + std::to_string(i) + " needs a noise draw the caller did not supply");
         if (!(steps[i].sqrt_recipm1_ac > 0.0f)) return fail(MTV_ERR_INVALID, "sqrt_recipm1_ac must be positive (pred_noise divides by it)");
     }
+    return MTV_OK;
+}
+
+int mtv_atom_ddim_sample(mtv_ctx* c, float* x_io, const float* face, const float* cond, const float* noise, int n_noise,
+                         const mtv_ddim_step* steps, int n_steps, int batch, void* stream) {
+    AtomState* A = atom_of(c);
+    int rc = atom_ready(c, A, batch);
+    if (rc != MTV_OK) return rc;
+    if ((rc = atom_check_sample(A, x_io, face, cond, noise, n_noise, steps, n_steps)) != MTV_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
     const size_t n = (size_t)batch * A->L * NFEAT;
@@ -980,6 +1012,45 @@ int mtv_atom_ddim_sample(mtv_ctx* c, float* x_io, const float* face, const float
     for (int i = 0; i < n_steps; ++i)
         if ((rc = atom_run(c, p, s)) != MTV_OK) return rc;
     HIPCHK(hipMemcpyAsync(x_io, A->x_io, n * 4, hipMemcpyDeviceToDevice, s));
+    return MTV_OK;
+}
+
+int mtv_atom_long_ddim_sample(mtv_ctx* c, float* x_io, const float* face, const float* cond, const float* noise, int n_noise,
+                              const mtv_ddim_step* steps, int n_steps, const float* weights, int batch, void* stream) {
+    AtomState* A = atom_of(c);
+    int rc = atom_ready(c, A, batch);
+    if (rc != MTV_OK) return rc;
+    if (batch < 2) return fail(MTV_ERR_INVALID, "the long sampler needs at least 2 windows (one window is mtv_atom_ddim_sample)");
+    if (A->L % 2) return fail(MTV_ERR_INVALID, "the long sampler needs an even seq_len (windows overlap by half)");
+    if ((rc = atom_check_sample(A, x_io, face, cond, noise, n_noise, steps, n_steps)) != MTV_OK) return rc;
+    if (!weights) return fail(MTV_ERR_INVALID, "null guidance weight table");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n = (size_t)batch * A->L * NFEAT;
+    HIPCHK(hipMemcpyAsync(A->x_io, x_io, n * 4, hipMemcpyDeviceToDevice, s));
+    A->h_steps.resize(n_steps);
+    std::memcpy(A->h_steps.data(), steps, (size_t)n_steps * sizeof(DdimStep));
+    HIPCHK(hipMemcpyAsync(A->steps, A->h_steps.data(), (size_t)n_steps * sizeof(DdimStep), hipMemcpyHostToDevice, s));
+    A->h_gws.assign(weights, weights + n_steps);
+    HIPCHK(hipMemcpyAsync(A->gws, A->h_gws.data(), (size_t)n_steps * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(A->counter, 0, sizeof(int), s));
+    if ((rc = atom_write_cur(A, 0.0f, 1, noise, (long long)n, s)) != MTV_OK) return rc;      // (gw: k_atom_advance writes the step's)
+    HIPCHK(atom_setup(*A, batch, DROP_PAIR, face, cond, s));
+    Plan* p[2] = {nullptr, nullptr};
+    if ((rc = atom_plan(c, A, batch, ATOM_LONG0, &p[0])) != MTV_OK || (rc = atom_plan(c, A, batch, ATOM_LONG1, &p[1])) != MTV_OK) return rc;
+    for (int i = 0; i < n_steps; ++i)      // step i reads the buffer step i - 1 wrote
+        if ((rc = atom_run(c, p[i & 1], s)) != MTV_OK) return rc;
+    HIPCHK(hipMemcpyAsync(x_io, n_steps & 1 ? A->x_alt : A->x_io, n * 4, hipMemcpyDeviceToDevice, s));
+    return MTV_OK;
+}
+
+int mtv_atom_long_num_launches(mtv_ctx* c, int batch, int* per_step) {
+    AtomState* A = atom_of(c);
+    if (!A || !per_step) return fail(MTV_ERR_INVALID, "not an AToM context");
+    Plan* p = nullptr;
+    int rc = atom_plan(c, A, batch, ATOM_LONG0, &p);
+    if (rc != MTV_OK) return rc;
+    *per_step = (int)p->ops.size();
     return MTV_OK;
 }
 

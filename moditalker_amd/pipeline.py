@@ -204,6 +204,72 @@ def audio_to_motion(hubert, first_frame_kpts, diffusion, key_mean_shape, save_di
     return out
 
 
+def hubert_windows(hubert, horizon: int) -> np.ndarray:
+    """HuBERT features [rows, feat] (two rows per video frame) of audio of any length -> [B, 2 horizon, feat], the
+    conditions of B half-overlapping windows of `horizon` frames: window b = rows [b horizon, b horizon + 2 horizon), the
+    slicing of AToM/inference.py:130 at a stride of half a horizon of frames.  F = rows // 2 frames need
+    B = 1 + ceil(max(0, F - horizon) / (horizon / 2)) windows; the (B + 1) horizon rows they read are made by repeating the
+    last row."""
+    h = np.asarray(hubert)
+    horizon = int(horizon)
+    if h.ndim != 2 or h.shape[0] < 2:
+        raise ValueError(f"hubert must be [rows >= 2, feature_dim]; got {h.shape}")
+    if horizon < 2 or horizon % 2:
+        raise ValueError(f"the horizon must be even (windows overlap by half); got {horizon}")
+    F = h.shape[0] // 2
+    B = 1 + -(-max(0, F - horizon) // (horizon // 2))
+    need = (B + 1) * horizon
+    if h.shape[0] < need:
+        h = np.concatenate([h, np.repeat(h[-1:], need - h.shape[0], axis=0)], axis=0)
+    return np.stack([h[b * horizon: b * horizon + 2 * horizon] for b in range(B)], axis=0)
+
+
+def merge_windows(samples) -> np.ndarray:
+    """[B, H, 204] half-overlapping windows -> one sequence [(B + 1) H / 2, 204]: the first half of window 0 and the last
+    half of window B - 1 as they are, every overlap a linear cross-fade, np.linspace(1, 0, H / 2) on the outgoing window and
+    np.linspace(0, 1, H / 2) on the incoming one.  The reference has no merge (its driver never reaches the long sampler); this
+    is EDGE's rule for positional channels, and landmarks are positions.  The sampler has already forced the overlaps to
+    agree at every step but the last, so the fade only blends what the final step changed."""
+    x = np.asarray(samples, dtype=np.float32)
+    if x.ndim != 3 or x.shape[1] % 2:
+        raise ValueError(f"samples must be [B, even H, C]; got {x.shape}")
+    B, H, _ = x.shape
+    half = H // 2
+    out = np.empty(((B + 1) * half, x.shape[2]), dtype=np.float32)
+    out[:half] = x[0, :half]
+    out[B * half:] = x[B - 1, half:]
+    fade_out = np.linspace(1, 0, half, dtype=np.float32)[:, None]
+    fade_in = np.linspace(0, 1, half, dtype=np.float32)[:, None]
+    for b in range(1, B):
+        out[b * half: (b + 1) * half] = x[b - 1, half:] * fade_out + x[b, :half] * fade_in
+    return out
+
+
+@torch.no_grad()
+def audio_to_motion_long(hubert, first_frame_kpts, diffusion, key_mean_shape, save_dir: Optional[str] = None, noise=None) -> np.ndarray:
+    """AToM for audio of any length: hubert_windows -> GaussianDiffusion.long_ddim_sample (AToM/model/diffusion.py:252-301)
+    -> merge_windows -> the arithmetic of audio_to_motion ((sample + face) / 10 + mean shape), trimmed to the
+    F = rows // 2 frames the audio has.  Arguments as audio_to_motion; `noise` is [1 + 49, B, horizon, 204] for the
+    B windows hubert_windows makes.  Returns [F, 68, 3] float32 and, with save_dir, writes <save_dir>/atom_long.npy."""
+    horizon = int(diffusion.horizon)
+    dev = diffusion.betas.device
+    kp = torch.as_tensor(np.asarray(first_frame_kpts), dtype=torch.float32).reshape(1, 1, -1)
+    if kp.shape[-1] != 204:
+        raise ValueError(f"first_frame_kpts must hold 68 x 3 values; got {kp.shape[-1]}")
+    cond = torch.from_numpy(np.ascontiguousarray(hubert_windows(hubert, horizon), dtype=np.float32))
+    B, F = cond.shape[0], int(np.asarray(hubert).shape[0]) // 2
+    face = kp.repeat(B, horizon, 1)
+    pos = torch.zeros(B, horizon, 3)
+    out = diffusion.long_ddim_sample((B, horizon, 204), face.to(dev), pos, cond.to(dev), noise=noise).detach().cpu().float()
+    out = torch.from_numpy(merge_windows(out.numpy()))[:F]
+    out = (out + kp[0]) / 10 + torch.as_tensor(np.asarray(key_mean_shape), dtype=torch.float32).reshape(1, 204)
+    out = out.reshape(F, 68, 3).numpy().astype(np.float32)
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        np.save(os.path.join(save_dir, "atom_long.npy"), out)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # the chunk loop (sample.py:305-400)
 # ------------------------------------------------------------------------------------------------------------------
