@@ -359,6 +359,57 @@ int mtv_atom_long_ddim_sample(mtv_ctx* ctx, float* x_io, const float* face, cons
 /* Launches of one step of the long sampler at this batch size: the same chain as mtv_atom_num_launches reports. */
 int mtv_atom_long_num_launches(mtv_ctx* ctx, int batch, int* per_step);
 
+/* ------------------------------------------------------------------------------------------------
+ * The stage in front of AToM: HuBERT audio features (csrc/hubert.hip).  Replaces the HubertModel.forward calls and the
+ * Wav2Vec2FeatureExtractor normalisation of data/data_utils/preprocess/process_audio.py:9-55: a 16 kHz waveform in,
+ * last_hidden_state [batch, T, hidden] out.  The stable-layer-norm form with layer-normed conv layers (the "large" family):
+ * conv feature encoder -> LayerNorm + projection -> x + GELU(grouped positional conv(x)) -> n_layers of
+ * x += attn(LN x); x += W2 gelu(W1 LN x) -> LayerNorm.  A separate context of the same opaque type: weights go in through
+ * mtv_num_weights / mtv_weight_info / mtv_load_weight / mtv_weights_missing with transformers' HubertModel state_dict keys
+ * (e.g. "encoder.layers.0.attention.q_proj.weight" [hidden, hidden]; the positional conv as
+ * "encoder.pos_conv_embed.conv.parametrizations.weight.original0" [1, 1, taps] (g) and "...original1" [hidden, hidden / groups, taps]
+ * (v): the effective weight v g / |v| is formed once after a load, not per call).  All tensors are device pointers.
+ * ------------------------------------------------------------------------------------------------ */
+#define MTV_HUBERT_MAX_CONV 8
+typedef struct mtv_hubert_config {
+    int32_t hidden;                             /* 1024; multiple of 4                                      */
+    int32_t n_layers;                           /* 24                                                       */
+    int32_t heads;                              /* 16; head dim a multiple of 4, at most 64                 */
+    int32_t intermediate;                       /* 4096; multiple of 4                                      */
+    int32_t n_conv;                             /* 7                                                        */
+    int32_t conv_dim[MTV_HUBERT_MAX_CONV];      /* 512 each; multiples of 4                                 */
+    int32_t conv_kernel[MTV_HUBERT_MAX_CONV];   /* 10, 3, 3, 3, 3, 2, 2                                     */
+    int32_t conv_stride[MTV_HUBERT_MAX_CONV];   /* 5, 2, 2, 2, 2, 2, 2                                      */
+    int32_t pos_taps;                           /* 128 (an even count drops the last output: T rows out)    */
+    int32_t pos_groups;                         /* 16; hidden / groups a multiple of 4                      */
+    float eps;                                  /* 1e-5: feature projection and encoder LayerNorms          */
+    int32_t max_samples;                        /* longest clip a forward may be given (320080)             */
+    int32_t max_batch;
+} mtv_hubert_config;
+int mtv_hubert_create(const mtv_hubert_config* cfg, mtv_ctx** out);
+int mtv_hubert_destroy(mtv_ctx* ctx);
+/* Wav2Vec2FeatureExtractor's do_normalize: out = (wave - mean) / sqrt(var + 1e-7) over all n samples (biased variance), any n >= 1.
+ * Two fixed-order reduction passes (fp64 partial sums, no atomics), then the map: a repeated call is bit-equal.  out may be wave. */
+int mtv_hubert_normalize(mtv_ctx* ctx, const float* wave, int64_t n, float* out, void* stream);
+/* Frames of a clip of n_samples: (n - k) / s + 1 through every conv layer; 0 when a layer has no valid window.  The context-free
+ * form below is the published geometry (10,3,3,3,3,2,2 / 5,2,2,2,2,2,2). */
+int mtv_hubert_frames(const mtv_ctx* ctx, int n_samples);
+int mtv_hubert_num_frames(int n_samples);
+/* wave [batch, n_samples] (normalised; clips of one length) -> out [batch, T, hidden], T = mtv_hubert_frames(n_samples).
+ * One linear chain of launches on `stream`; argument errors (T = 0, n_samples > max_samples, batch > max_batch, missing weights)
+ * are reported before anything is launched. */
+int mtv_hubert_forward(mtv_ctx* ctx, const float* wave, int n_samples, int batch, float* out, void* stream);
+/* Launches of one forward at this clip length and batch. */
+int mtv_hubert_num_launches(mtv_ctx* ctx, int n_samples, int batch, int* n_out);
+/* Per-launch hipEvent timing of that forward, like mtv_ae_profile (out == NULL: only the count); the result is discarded. */
+int mtv_hubert_profile(mtv_ctx* ctx, const float* wave, int n_samples, int batch, int iters, mtv_op_time* out, int cap, int* n_out,
+                       void* stream);
+/* keep != 0: every later forward also keeps copies of two tensors it otherwise updates in place ("after_pos_conv", "layer_0").
+ * mtv_hubert_debug_tap reads a tensor of the LAST forward: those two, or "extract_features" (the conv encoder's output,
+ * [batch, T, conv_dim[n_conv - 1]]).  dst: host or device, cap floats; rows_out = batch T of that forward. */
+int mtv_hubert_debug_keep(mtv_ctx* ctx, int keep);
+int mtv_hubert_debug_tap(mtv_ctx* ctx, const char* name, float* dst, int64_t cap, int* rows_out, int* channels_out);
+
 #ifdef __cplusplus
 }
 #endif

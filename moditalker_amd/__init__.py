@@ -8,6 +8,7 @@ from .unet import DiffusionWrapper, UNetModel  # noqa: F401
 from .autoencoder import ViTAutoencoder  # noqa: F401
 from .cross_attention import CrossAttention  # noqa: F401
 from .atom import GaussianDiffusion, MotionDecoder  # noqa: F401
+from .hubert import HUBERT_LARGE_CONFIG, HubertModel  # noqa: F401
 
 ATOM_CONFIG = dict(  # AToM/AToM.py:57-81: the decoder and the diffusion around it (horizon 156, HuBERT features)
     nfeats=204, seq_len=156, latent_dim=512, ff_size=1024, num_layers=8, num_heads=8, dropout=0.1, cond_feature_dim=1024,

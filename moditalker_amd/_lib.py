@@ -53,6 +53,12 @@ class MtvAtomConfig(C.Structure):
                                          "max_batch")]
 
 
+class MtvHubertConfig(C.Structure):
+    _fields_ = [("hidden", C.c_int32), ("n_layers", C.c_int32), ("heads", C.c_int32), ("intermediate", C.c_int32), ("n_conv", C.c_int32),
+                ("conv_dim", C.c_int32 * 8), ("conv_kernel", C.c_int32 * 8), ("conv_stride", C.c_int32 * 8), ("pos_taps", C.c_int32),
+                ("pos_groups", C.c_int32), ("eps", C.c_float), ("max_samples", C.c_int32), ("max_batch", C.c_int32)]
+
+
 class MtvDdimStep(C.Structure):
     _fields_ = [
         ("t", C.c_int32),
@@ -132,6 +138,16 @@ SYMBOLS = [
     ("mtv_atom_num_launches", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     ("mtv_atom_long_ddim_sample", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(MtvDdimStep), C.c_int, C.POINTER(C.c_float), C.c_int, _P]),
     ("mtv_atom_long_num_launches", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("mtv_hubert_create", C.c_int, [C.POINTER(MtvHubertConfig), C.POINTER(_P)]),
+    ("mtv_hubert_destroy", C.c_int, [_P]),
+    ("mtv_hubert_normalize", C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    ("mtv_hubert_frames", C.c_int, [_P, C.c_int]),
+    ("mtv_hubert_num_frames", C.c_int, [C.c_int]),
+    ("mtv_hubert_forward", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    ("mtv_hubert_num_launches", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    ("mtv_hubert_profile", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(MtvOpTime), C.c_int, C.POINTER(C.c_int), _P]),
+    ("mtv_hubert_debug_keep", C.c_int, [_P, C.c_int]),
+    ("mtv_hubert_debug_tap", C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mtv_selftest_geometry", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_deep", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_block", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

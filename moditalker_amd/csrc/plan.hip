@@ -1572,6 +1572,7 @@ int mtv_load_weight(mtv_ctx* c, const char* key, const float* data, int ndim, co
         HIPCHK(hipStreamSynchronize(nullptr));
     }
     s.loaded = true;
+    ++c->load_serial;
     for (auto& kv : c->w3) kv.second.dirty = true;      // (rebuilt before the next run: check_ready)
     for (auto& kv : c->wdeep) kv.second.dirty = true;
     return MTV_OK;

@@ -130,7 +130,7 @@ struct Plan {
 };
 
 
-enum CtxKind { CTX_UNET = 0, CTX_AE = 1, CTX_XATTN = 2, CTX_ATOM = 3 };
+enum CtxKind { CTX_UNET = 0, CTX_AE = 1, CTX_XATTN = 2, CTX_ATOM = 3, CTX_HUBERT = 4 };
 
 struct mtv_ctx {
     mtv_config cfg{};
@@ -147,6 +147,7 @@ struct mtv_ctx {
 
     std::vector<WSlot> slots;
     std::map<std::string, int> slot_index;
+    unsigned load_serial = 0;                   // + 1 per mtv_load_weight: a context that derives matrices from several keys (hubert.hip) rebuilds them when it moved
     std::map<std::string, float*> bufs;         // named activation / weight buffers
     std::map<std::string, size_t> buf_floats;   // ... and the size each was allocated with
     std::map<std::string, std::pair<int, int>> taps;   // tap name -> (level, C) ; buffer = bufs["tap." + name]

@@ -271,6 +271,71 @@ def audio_to_motion_long(hubert, first_frame_kpts, diffusion, key_mean_shape, sa
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# the stage in front of the stage in front: waveform -> HuBERT features (data/data_utils/preprocess/process_audio.py:9-55)
+# ------------------------------------------------------------------------------------------------------------------
+HUBERT_KERNEL, HUBERT_STRIDE = 400, 320                  # receptive field and hop of the conv encoder, in samples
+HUBERT_CLIP_LENGTH = HUBERT_STRIDE * 1000                 # process_audio.py:26: 20 s of 16 kHz audio per clip
+
+
+@torch.no_grad()
+def audio_to_hubert(speech, model, save_path: Optional[str] = None) -> np.ndarray:
+    """get_hubert_from_speech (process_audio.py:9-55) step for step, on moditalker_amd.HubertModel.
+      speech   the utterance at 16 kHz, [N] or [N, channels] (channel 0 is kept).  Resampling to 16 kHz is ffmpeg in the
+               reference (process_audio.py:57-64) and stays with the caller.
+      model    anything with HubertModel's forward: forward(input_values [B, n]).last_hidden_state is [B, T, hidden].  If it
+               has `normalize` (HubertModel: the device reduction) that normalises the utterance, else the same formula in
+               numpy -- which is there so that the windowing can be tested on the CPU with a stub, not as a product path.
+    The WHOLE utterance is normalised first ((x - mean) / sqrt(var + 1e-7), Wav2Vec2FeatureExtractor); clip i is samples
+    [i 320000, i 320000 + 320080), the remainder starts at num_iter 320000 and is skipped below 400 samples; the clips'
+    features are concatenated and padded with zero rows or trimmed to expected_T = (N - 80) // 320, ValueError when they
+    differ by more than one row (the reference's assert).  Clips of equal length go through the model as one batch of up to
+    model.max_batch clips (every kernel works per clip: the rows are those of one-by-one calls).
+    Returns [expected_T, hidden] float32 -- what audio_to_motion / audio_to_motion_long take -- and, with save_path, np.save's it."""
+    x = np.asarray(speech.detach().cpu() if torch.is_tensor(speech) else speech)
+    if x.ndim == 2:
+        x = x[:, 0]
+    if x.ndim != 1 or x.shape[0] < 1:
+        raise ValueError(f"speech must be [N] or [N, channels]; got {x.shape}")
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if hasattr(model, "normalize"):
+        values = torch.as_tensor(model.normalize(x))
+    else:
+        values = torch.from_numpy(((x - x.mean()) / np.sqrt(x.var() + 1e-7)).astype(np.float32))
+    N = int(values.shape[0])
+    num_iter = N // HUBERT_CLIP_LENGTH
+    expected_T = (N - (HUBERT_KERNEL - HUBERT_STRIDE)) // HUBERT_STRIDE
+    spans = [(i * HUBERT_CLIP_LENGTH, min(N, i * HUBERT_CLIP_LENGTH + HUBERT_CLIP_LENGTH - HUBERT_STRIDE + HUBERT_KERNEL)) for i in range(num_iter)]
+    rest = (num_iter * HUBERT_CLIP_LENGTH, N)
+    if rest[1] - rest[0] >= HUBERT_KERNEL:             # a remainder shorter than the receptive field is skipped
+        spans.append(rest)
+    cap = max(1, int(getattr(model, "max_batch", 1)))
+    res: List[torch.Tensor] = []
+    i = 0
+    while i < len(spans):
+        j = i + 1
+        while j < len(spans) and j - i < cap and spans[j][1] - spans[j][0] == spans[i][1] - spans[i][0]:
+            j += 1
+        batch = torch.stack([values[a:b] for a, b in spans[i:j]])
+        hidden = model.forward(batch).last_hidden_state
+        res.extend(torch.as_tensor(hidden[b]).detach().cpu().float() for b in range(j - i))
+        i = j
+    if not res:
+        raise ValueError(f"speech has {N} samples; one feature row needs {HUBERT_KERNEL}")
+    ret = torch.cat(res, dim=0)
+    if abs(ret.shape[0] - expected_T) > 1:
+        raise ValueError(f"the clips gave {ret.shape[0]} rows, {expected_T} expected from {N} samples")
+    if ret.shape[0] < expected_T:
+        ret = torch.nn.functional.pad(ret, (0, 0, 0, expected_T - ret.shape[0]))
+    else:
+        ret = ret[:expected_T]
+    out = ret.numpy().astype(np.float32)
+    if save_path is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(save_path)), exist_ok=True)
+        np.save(save_path, out)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # the chunk loop (sample.py:305-400)
 # ------------------------------------------------------------------------------------------------------------------
 class MToVSampler:
