@@ -246,6 +246,12 @@ int mtv_selftest_block(int tokens, int channels, int heads, int batch);
  * the source tensor and contains the source token of every tap of every output row (the taps of mtv_debug_gather_index).  0 = ok,
  * else 1 + the first level that fails (<0: bad arguments). */
 int mtv_selftest_win(int res, int frames, int n_levels);
+/* Host-only self-test of k_conv_win's packed weight operand (csrc/deep.hip, csrc/mtv_internal.h WinPack: the 3x3 conv matrix -- unet.py:131-167 in_layers /
+ * out_layers, with the fused 1x1 skip_connection of :169-176 -- rewritten per (column tile, K slice, wave) in the order the kernel's K loop consumes it).  For the
+ * tile <mt, nt> with ks K slices and a conv of cmain tapped + cskip fused-skip input channels and n output channels: the packed-index -> (row, column) map reaches
+ * every element of the matrix exactly once, every other packed position is zero padding (the chunks past a wave's last), and the offsets the kernel computes land on
+ * the elements its MFMA operand registers expect.  0 = ok, > 0: the violated invariant, < 0: bad arguments (a tile that does not exist, a shape it cannot slice). */
+int mtv_selftest_win_pack(int mt, int nt, int ks, int cmain, int cskip, int n);
 /* The arithmetic itself, for tests: source token of tap (ky, kx in 0..2) at output token `tok` of a level with
  * planes res x res | frames x res | frames x res; up != 0: the source is the (res/2, frames/2) level under a
  * nearest x2 upsample.  Returns -1 for zero padding, else source_token | plane << 28. */

@@ -152,6 +152,7 @@ SYMBOLS = [
     ("mtv_selftest_deep", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_block", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_win", C.c_int, [C.c_int, C.c_int, C.c_int]),
+    ("mtv_selftest_win_pack", C.c_int, [C.c_int] * 6),
     ("mtv_debug_gather_index", C.c_int, [C.c_int] * 6),
     ("mtv_check_fault", C.c_int, [_P]),
     ("mtv_resident_cus", C.c_int, [_P]),

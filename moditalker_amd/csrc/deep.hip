@@ -677,6 +677,14 @@ __global__ void k_deep_repack(const float* W, int ldw, float* dst, DeepArgs a, i
     dst[id] = W[(size_t)krow * ldw + (j * NT + nt) * 16 + jj];
 }
 
+// legacy conv matrix [krow][ldw] -> k_conv_win's packed operand (WinPack, mtv_internal.h): one thread per destination float, padding written as zero
+__global__ void k_win_repack(const float* W, int ldw, float* dst, WinPack p, size_t total) {
+    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= total) return;
+    int krow, col;
+    dst[id] = win_pack_source(p, id, &krow, &col) ? W[(size_t)krow * ldw + col] : 0.f;
+}
+
 // slabs -> plain tensor (+ GroupNorm statistics for legacy consumers, conv.hip / k_pool_down).  Grid: (channel blocks of 64,
 // token blocks of 8, clips) -- wide on purpose: the pass is a latency chain (slab loads -> sum -> store), so it wants every CU
 // to hold a few quads, not a few CUs to hold everything.  64 channels x 8 tokens = 128 quads per workgroup of 128 threads.
@@ -1118,7 +1126,8 @@ __global__ __launch_bounds__(DEEP_NTH) void k_deep_attn(const DeepAttnArgs a) {
 // the K loop, on the VALU that the exact-f32 MFMA blocks (conv.hip section 3.1: K loop 630 us per step for 364 us of MFMA).
 // Workgroup = (clip, row tile, column tile of 16 NT channels), 512 threads; the 8 waves split K (chunk c -> wave c mod 8), B
 // fragments straight from k_conv's weight layout (lane (j, q) loads W[c0 + 4q + s][n0 + NT j ..+NT-1]: output channel
-// n0 + NT j + nb sits at lane j of column block nb), summed in wave order through LDS.
+// n0 + NT j + nb sits at lane j of column block nb) or, PK (round 9, the product's default), the same values from the copy packed in the
+// loop's own order (ConvArgs::Wwin), summed in wave order through LDS.
 // Source-token window of the row tile that starts at output token tok0 (a superset of what its taps touch, one contiguous range:
 // planes are contiguous and a 3x3 tap moves at most one image row + one token).  Host (LDS sizing) and device use the same code.
 __host__ __device__ inline void conv_win_window(int r, int t, bool up, int Lout, int tok0, int rows, int* lo, int* n) {
@@ -1145,7 +1154,7 @@ __host__ __device__ inline void conv_win_window(int r, int t, bool up, int Lout,
     *n = whi - wlo + 1;
 }
 
-template <int MT, int NT>
+template <int MT, int NT, bool PK>
 __global__ __launch_bounds__(DEEP_NTH) void k_conv_win(const ConvArgs a) {
     touch_kernargs<(int)sizeof(ConvArgs)>();
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1259,11 +1268,29 @@ __global__ __launch_bounds__(DEEP_NTH) void k_conv_win(const ConvArgs a) {
     const int cpt = a.cpt, nmain_ch = 9 * cpt, nch = nmain_ch + (Css >> 4);
     const int n_it = (nch + 7) >> 3;
     const int wrows = 9 * Cmain + Cskip;
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W), 0, wrows * a.ldw * 4, 0x00020000);
-    const int wlane = ((4 * q) * a.ldw + n0 + NT * i) * 4;
+    // PK (round 9): the weights come from ConvArgs::Wwin, the matrix in this loop's own order (WinPack, mtv_internal.h): the chunks of this (column tile, K slice,
+    // wave) are one run, NT KB each -- a chunk is NT 16-byte requests per lane, a contiguous KB per request, at run base + kc x a constant; no tap decode, no
+    // division, no row stride.  Same values in the same registers as the legacy reads below, so nothing after the loads knows the difference.
+    const __amdgpu_buffer_rsrc_t wrsrc = PK ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Wwin), 0, a.tiles_n * KS * 8 * n_it * (NT * 1024), 0x00020000)
+                                            : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W), 0, wrows * a.ldw * 4, 0x00020000);
+    const int wlane = PK ? lane * 16 : ((4 * q) * a.ldw + n0 + NT * i) * 4;
+    const int wrun = deep_usgpr(((ct * KS + z) * 8 + wave) * n_it * (NT * 1024));       // (PK: byte offset of this wave's run; < 0x7F000000, conv_win_eligible)
     bvec bq[2][G][4];
     auto wload1 = [&](bvec (&dstg)[4], int kc) {
-        {
+        if constexpr (PK) {
+            // a chunk past the run reads out of range = zeros (the bytes behind a run are the next run's); the run's own padding chunks hold zeros
+            const int soff = kc < n_it ? wrun + kc * (NT * 1024) : 0x7F000000;
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane + j * 1024, soff, 0));
+                if constexpr (NT == 4) {
+                    dstg[j] = v;
+                } else {
+                    dstg[2 * j] = bvec{v[0], v[1]};
+                    dstg[2 * j + 1] = bvec{v[2], v[3]};
+                }
+            }
+        } else {
             const int c = wave + 8 * kc;
             // W row of the chunk's first channel: tap-major over the concatenated main channels, then the skip channels (k_conv's
             // order of rows); a chunk past the end reads out of range = zeros
@@ -2056,8 +2083,10 @@ hipError_t deep_init_attrs() {
     }
     const void* fa[] = {reinterpret_cast<const void*>(&k_deep_attn<16>), reinterpret_cast<const void*>(&k_deep_attn<32>), reinterpret_cast<const void*>(&k_deep_attn<64>),
                         reinterpret_cast<const void*>(&k_deep_attn<128>),
-                        reinterpret_cast<const void*>(&k_conv_win<1, 4>), reinterpret_cast<const void*>(&k_conv_win<1, 2>),
-                        reinterpret_cast<const void*>(&k_conv_win<2, 2>), reinterpret_cast<const void*>(&k_conv_win<2, 4>),
+                        reinterpret_cast<const void*>(&k_conv_win<1, 4, false>), reinterpret_cast<const void*>(&k_conv_win<1, 2, false>),
+                        reinterpret_cast<const void*>(&k_conv_win<2, 2, false>), reinterpret_cast<const void*>(&k_conv_win<2, 4, false>),
+                        reinterpret_cast<const void*>(&k_conv_win<1, 4, true>), reinterpret_cast<const void*>(&k_conv_win<1, 2, true>),
+                        reinterpret_cast<const void*>(&k_conv_win<2, 2, true>), reinterpret_cast<const void*>(&k_conv_win<2, 4, true>),
                         reinterpret_cast<const void*>(&k_conv_pw<1, 1, 8>), reinterpret_cast<const void*>(&k_conv_pw<1, 2, 8>),
                         reinterpret_cast<const void*>(&k_conv_pw<2, 1, 8>), reinterpret_cast<const void*>(&k_conv_pw<2, 2, 8>),
                         reinterpret_cast<const void*>(&k_conv_pw<1, 1, 6>), reinterpret_cast<const void*>(&k_conv_pw<2, 1, 6>),
@@ -2068,6 +2097,13 @@ hipError_t deep_init_attrs() {
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_win_repack(const float* W, int ldw, float* dst, const WinPack& p, hipStream_t s) {
+    if (!win_pack_valid(p) || p.N > ldw) return hipErrorInvalidValue;
+    const size_t total = win_pack_floats(p);
+    hipLaunchKernelGGL(k_win_repack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, W, ldw, dst, p, total);
+    return hipGetLastError();
 }
 
 hipError_t launch_deep_repack(const float* W, int ldw, float* dst, const DeepArgs& a0, int NT, hipStream_t s) {
@@ -2225,14 +2261,71 @@ bool conv_win_eligible(const ConvArgs& a, int MT, int NT, int KS) {
     for (int t = 0; t < a.nstat; ++t)
         if (a.stat[t].coff & 3) return false;
     if ((long)(9 * a.Cmain + a.Cskip) * a.ldw * 4 >= 0x7F000000L) return false;
+    // a packed copy (ConvArgs::Wwin) serves ONE (NT, KS): another tile must not read it (the plan attaches it to the tile an op finally runs on, and the tuner
+    // times its candidates without one)
+    if (a.Wwin) {
+        const WinPack p{NT, KS, a.Cmain, a.Cskip, a.N};
+        if (a.wwin_shape != 16 * NT + KS || !win_pack_valid(p)) return false;       // (the kernel sizes its descriptor by win_pack_floats of this shape)
+    }
     return conv_win_layout(a, MT, NT, KS, nullptr) <= 160 * 1024;
+}
+// a shape k_win_repack can pack: what conv_win_eligible asks of (NT, KS, Cmain, Cskip, N)
+bool win_pack_valid(const WinPack& p) {
+    return (p.NT == 2 || p.NT == 4) && (p.KS == 1 || p.KS == 2 || p.KS == 4) && p.Cmain >= 16 && p.Cskip >= 0 && p.N >= 16 * p.NT &&
+           !(p.Cmain & 15) && !(p.Cskip & 15) && !((p.Cmain / 16) % p.KS) && !((p.Cskip / 16) % p.KS) && !(p.N % (16 * p.NT)) &&
+           win_pack_floats(p) * 4 < 0x7F000000UL;
+}
+// Host-only check of win_pack_source (the map k_win_repack writes by): every legacy element of rows [0, 9 Cmain + Cskip) x columns [0, N) is the source of
+// exactly one packed position, every other packed position is padding, the padding is exactly the chunks at or past nch of each (tile, slice, wave) run, and
+// the position the KERNEL's load arithmetic gives for (tile, slice, wave, chunk, load, lane) maps back to the B-fragment element that load feeds.  0 = ok.
+int win_pack_selftest(const WinPack& p) {
+    if (!win_pack_valid(p)) return 1;
+    const int rows = 9 * p.Cmain + p.Cskip, n_it = win_pack_nit(p), nch = win_pack_nch(p);
+    const size_t total = win_pack_floats(p);
+    std::vector<unsigned char> seen((size_t)rows * p.N, 0);
+    size_t pads = 0;
+    for (size_t id = 0; id < total; ++id) {
+        int krow = -1, col = -1;
+        if (!win_pack_source(p, id, &krow, &col)) { ++pads; continue; }
+        if (krow < 0 || krow >= rows || col < 0 || col >= p.N) return 2;
+        if (seen[(size_t)krow * p.N + col]++) return 3;
+    }
+    for (unsigned char v : seen)
+        if (v != 1) return 4;
+    const int tiles_n = p.N / (16 * p.NT);
+    size_t pads_expected = 0;
+    for (int w = 0; w < 8; ++w)
+        for (int kc = 0; kc < n_it; ++kc)
+            if (w + 8 * kc >= nch) pads_expected += (size_t)p.NT * 256;
+    if (pads != pads_expected * tiles_n * p.KS) return 5;
+    // the kernel's side: byte offset = run base + kc x NT KB + j KB + 16 lane (k_conv_win, PK), element e of that quad -> register (sI, nb) of lane (i, q)
+    const int Cs = p.Cmain / p.KS, Css = p.Cskip / p.KS, cpt = Cs / 16;
+    for (int ct = 0; ct < tiles_n; ++ct)
+        for (int z = 0; z < p.KS; ++z)
+            for (int w = 0; w < 8; ++w)
+                for (int kc = 0; kc < n_it; ++kc)
+                    for (int j = 0; j < p.NT; ++j)
+                        for (int lane = 0; lane < 64; ++lane)
+                            for (int e = 0; e < 4; ++e) {
+                                const size_t byte = (size_t)((ct * p.KS + z) * 8 + w) * n_it * (p.NT * 1024) + (size_t)kc * (p.NT * 1024) + j * 1024 + lane * 16 + e * 4;
+                                const int c = w + 8 * kc, i = lane & 15, q = lane >> 4;
+                                const int sI = p.NT == 4 ? j : 2 * j + (e >> 1), nb = p.NT == 4 ? e : (e & 1);
+                                int krow = -1, col = -1;
+                                const bool live = win_pack_source(p, byte / 4, &krow, &col);
+                                if (live != (c < nch)) return 6;
+                                if (!live) continue;
+                                int k0 = 9 * p.Cmain + z * Css + (c - 9 * cpt) * 16;             // (the legacy reads' row of the chunk: wload1)
+                                if (c < 9 * cpt) { const int tap = c / cpt; k0 = tap * p.Cmain + z * Cs + (c - tap * cpt) * 16; }
+                                if (krow != k0 + 4 * q + sI || col != 16 * p.NT * ct + p.NT * i + nb) return 7;
+                            }
+    return 0;
 }
 bool conv_win_can_run(const ConvArgs& a, const ConvTile& t, size_t slab_cap) {
     return conv_win_tile_exists(t) && conv_win_eligible(a, t.MT, t.NT, t.KS) && conv_slab_fits(a, t.KS, slab_cap);
 }
 size_t conv_win_smem_bytes(const ConvArgs& a, ConvTile t) { return conv_win_layout(a, t.MT, t.NT, t.KS < 1 ? 1 : t.KS, nullptr); }
 
-template <int MT, int NT>
+template <int MT, int NT, bool PK>
 static hipError_t conv_win_launch_t(const ConvArgs& a0, int xm, int KS, hipStream_t s) {
     ConvArgs a = a0;
     if (!conv_win_eligible(a, MT, NT, KS) || (KS > 1 && (!a.slab || !a.tickets))) return hipErrorInvalidValue;
@@ -2273,17 +2366,25 @@ static hipError_t conv_win_launch_t(const ConvArgs& a0, int xm, int KS, hipStrea
     const size_t smem = conv_win_layout(a, MT, NT, KS, &wcap);
     a.rec_cap = wcap;
     if ((long)a.Bt * tiles_n * KS >= (1L << 21)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_conv_win<MT, NT>), dim3((unsigned)(a.Bt * tiles_n * KS)), dim3(DEEP_NTH), smem, s, a);
+    if (PK != (a.Wwin != nullptr)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_conv_win<MT, NT, PK>), dim3((unsigned)(a.Bt * tiles_n * KS)), dim3(DEEP_NTH), smem, s, a);
     return hipGetLastError();
 }
 hipError_t launch_conv_win(const ConvArgs& a, ConvTile t, hipStream_t s) {
     static const int env_xm = getenv("MTV_WIN_XM") ? atoi(getenv("MTV_WIN_XM")) : -1;       // (A/B hook: block order of every k_conv_win launch)
     if (env_xm >= 0) t.XM = env_xm;
     const int KS = t.KS < 1 ? 1 : t.KS;
-    if (t.MT == 1 && t.NT == 4) return conv_win_launch_t<1, 4>(a, t.XM, KS, s);
-    if (t.MT == 1 && t.NT == 2) return conv_win_launch_t<1, 2>(a, t.XM, KS, s);
-    if (t.MT == 2 && t.NT == 2) return conv_win_launch_t<2, 2>(a, t.XM, KS, s);
-    if (t.MT == 2 && t.NT == 4) return conv_win_launch_t<2, 4>(a, t.XM, KS, s);
+    if (a.Wwin) {                                            // (conv_win_eligible: the copy is this tile's)
+        if (t.MT == 1 && t.NT == 4) return conv_win_launch_t<1, 4, true>(a, t.XM, KS, s);
+        if (t.MT == 1 && t.NT == 2) return conv_win_launch_t<1, 2, true>(a, t.XM, KS, s);
+        if (t.MT == 2 && t.NT == 2) return conv_win_launch_t<2, 2, true>(a, t.XM, KS, s);
+        if (t.MT == 2 && t.NT == 4) return conv_win_launch_t<2, 4, true>(a, t.XM, KS, s);
+        return hipErrorInvalidValue;
+    }
+    if (t.MT == 1 && t.NT == 4) return conv_win_launch_t<1, 4, false>(a, t.XM, KS, s);
+    if (t.MT == 1 && t.NT == 2) return conv_win_launch_t<1, 2, false>(a, t.XM, KS, s);
+    if (t.MT == 2 && t.NT == 2) return conv_win_launch_t<2, 2, false>(a, t.XM, KS, s);
+    if (t.MT == 2 && t.NT == 4) return conv_win_launch_t<2, 4, false>(a, t.XM, KS, s);
     return hipErrorInvalidValue;
 }
 

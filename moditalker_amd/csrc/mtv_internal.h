@@ -75,9 +75,13 @@ struct ConvArgs {
     int ntaps;
     int Lout, Lsrc, Lskip;   // tokens per batch element: output, tapped source, skip/residual source
     int B;
+    int KS;                  // >1: cross-workgroup split-K; partial tiles go to `slab`, the last slice completes  (here and wwin_shape below: in the alignment
+                             // holes in front of a pointer -- the block is exactly eight 64-byte lines, see the static_assert)
     const float* W;          // rows [ntaps*Cmain + Cskip][ldw], columns = output channels
     const float* Wpk;        // 1x1 convs on identity rows only (N, Cmain multiples of 16): k_conv_pw's operand [N / 16][Cmain / 16][64 lanes][4] -- lane (j, q) of (column
                              // block bn, chunk c) holds W[16 bn + j][16 c + 4 q .. + 3], so a wave's B fragment of a chunk is ONE contiguous KB (k_repack_pw, kernels.hip)
+    const float* Wwin;       // 3x3 convs on a k_conv_win tile: the conv matrix in the order that kernel walks it (WinPack below, k_win_repack in deep.hip), made for ONE
+                             // (NT, KS) -- wwin_shape = 16 NT + KS; nullptr: the kernel reads W
     const void* W3;          // the same matrix as three bf16 planes [3][K/8][ldw][8] with W = W0 + W1 + W2 (k_conv_x3, conv_x3.hip) or nullptr
     unsigned long long w3_plane;   // bytes between the planes
     void* x3;                // scratch for this conv's split activations (k_x3_prep -> k_conv_x3, conv_x3.hip) or nullptr
@@ -87,6 +91,7 @@ struct ConvArgs {
     const float* bias2;      // [N] or nullptr (bias of the fused skip conv)
     const float* bias_b;     // per-batch additive [B][bias_b_stride] or nullptr
     int bias_b_stride;
+    int wwin_shape;          // (Wwin above)
     GnIn gn;
     SegInfo seg_src;         // plane boundaries of the tapped source token axis
     const float* res;        // residual [B][Lskip][N] (identity skip) or nullptr
@@ -96,7 +101,6 @@ struct ConvArgs {
     StatOut stat[2];
     int nstat;
     unsigned stat_cstride;   // doubles between the copies of the statistics arena
-    int KS;                  // >1: cross-workgroup split-K; partial tiles go to `slab`, the last slice completes
     int* tickets;            // [B * row tiles * column tiles] arrival counters (zero between launches)
     float* slab;             // [KS][B][Lout][N]
     int xmap;                // ConvTile::XM
@@ -119,6 +123,42 @@ struct ConvArgs {
     unsigned long long* dbg; // phase timestamps for tools/ubench/conv_bench (nullptr in the product)
     long long dbg_stat_dup;  // 0 in the product: offset (doubles) of the other step parity's statistics arena (MTV_DEBUG_STATDUP timing experiment)
 };
+static_assert(sizeof(ConvArgs) <= 512, "touch_kernargs takes its eight-line form (profiles/r07_retire_k_lin_step_ab.txt: what a ninth line costs)");
+
+// k_conv_win's packed 3x3 operand (ConvArgs::Wwin): [column tile of 16 NT][K slice z][wave w][chunk kc < n_it][NT loads][64 lanes][4] -- the chunks
+// c = w + 8 kc of one (tile, slice, wave) in the order the K loop walks them (nine taps over the slice's tapped channels, then its fused-skip channels), every
+// run padded with zero chunks to n_it = ceil(nch / 8); a chunk is NT contiguous KB, one 16-byte request per lane and load.  Lane (i, q) of a chunk whose first
+// legacy row is krow0 holds, flat over (load j, element e), f = 4 j + e: W[krow0 + 4 q + f / NT][16 NT ct + NT i + f % NT] -- the kernel's B-fragment registers.
+struct WinPack { int NT, KS, Cmain, Cskip, N; };
+__host__ __device__ inline int win_pack_nch(const WinPack& p) { return 9 * (p.Cmain / p.KS / 16) + p.Cskip / p.KS / 16; }
+__host__ __device__ inline int win_pack_nit(const WinPack& p) { return (win_pack_nch(p) + 7) >> 3; }
+__host__ __device__ inline size_t win_pack_floats(const WinPack& p) { return (size_t)(p.N / (16 * p.NT)) * p.KS * 8 * win_pack_nit(p) * p.NT * 256; }
+// packed float index -> legacy (row, column) of ConvArgs::W; false: a padded position, which holds zero.  THE map: k_win_repack writes by it, mtv_selftest_win_pack
+// checks it, and the kernel's loads are its inverse
+__host__ __device__ inline bool win_pack_source(const WinPack& p, size_t id, int* krow, int* col) {
+    const int e = (int)(id & 3), lane = (int)((id >> 2) & 63), n_it = win_pack_nit(p);
+    size_t rest = id >> 8;
+    const int j = (int)(rest % p.NT);
+    rest /= p.NT;
+    const int kc = (int)(rest % n_it);
+    rest /= n_it;
+    const int w = (int)(rest & 7);
+    rest >>= 3;
+    const int z = (int)(rest % p.KS), ct = (int)(rest / p.KS);
+    const int Cs = p.Cmain / p.KS, Css = p.Cskip / p.KS, cpt = Cs / 16, c = w + 8 * kc;
+    if (c >= win_pack_nch(p)) return false;
+    int krow0;
+    if (c < 9 * cpt) {
+        const int tap = c / cpt;
+        krow0 = tap * p.Cmain + z * Cs + (c - tap * cpt) * 16;
+    } else {
+        krow0 = 9 * p.Cmain + z * Css + (c - 9 * cpt) * 16;
+    }
+    const int f = 4 * j + e, i = lane & 15, q = lane >> 4;
+    *krow = krow0 + 4 * q + f / p.NT;
+    *col = 16 * p.NT * ct + p.NT * i + f % p.NT;
+    return true;
+}
 
 // Touch every 64-byte line of the kernel-argument block at kernel entry.  The compiler otherwise loads
 // struct fields lazily, each first touch of a line being a scalar-cache miss that goes all the way to
@@ -492,6 +532,9 @@ bool conv_win_can_run(const ConvArgs& a, const ConvTile& t, size_t slab_cap);
 int conv_win_selftest(int r, int t, bool up, int Lout, int Lsrc);      // host-only check of the window arithmetic (0 = ok)
 size_t conv_win_smem_bytes(const ConvArgs& a, ConvTile t);
 hipError_t launch_conv_win(const ConvArgs& a, ConvTile t, hipStream_t s);
+bool win_pack_valid(const WinPack& p);
+int win_pack_selftest(const WinPack& p);                               // host-only check of win_pack_source against the kernel's load arithmetic (0 = ok)
+hipError_t launch_win_repack(const float* W, int ldw, float* dst, const WinPack& p, hipStream_t s);   // legacy [krow][ldw] -> ConvArgs::Wwin
 bool conv_pw_eligible(const ConvArgs& a, int MT, int NTW, int wcode = 1);     // wcode = ConvTile::KS of the tile: 1 = all 8 waves multiply, 6 / 4 / 2 = that many (column tile 16 NTW x waves)
 bool conv_pw_tile_exists(const ConvTile& t);
 bool conv_pw_can_run(const ConvArgs& a, const ConvTile& t, size_t slab_cap);

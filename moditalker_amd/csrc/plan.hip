@@ -304,6 +304,7 @@ struct Builder {
         op->a = a0;
         op->t = conv_pick_tile(B, a0.Lout, a0.N, nchunks, a0.Cmain, a0.gn.sums != nullptr);
         force_family_tile(a0, &op->t);
+        if (attach_win_pack(c, op.get()) != MTV_OK) err = "packed 3x3 weight copy failed at " + name;
         op->base_name = std::string(a0.ntaps == 9 ? "conv3:" : "conv1:") + name;
         op->op_index = (int)plan->ops.size();
         producer[a0.out] = op;
@@ -1060,6 +1061,23 @@ static bool deep_forced_off() {
     return g_force_lds.v[0] > 0 || force_env(g_force_b3).v[0] > 0 || getenv("MTV_FORCE_TILE") || getenv("MTV_FORCE_LDS");     // (not MTV_FORCE_WIN: k_conv_win serves
                                                                                                                              //  the large levels)
 }
+// k_conv_win's packed weight copy for the tile an op runs on (ConvArgs::Wwin; round 9): attached when the tile is final -- the builder's (a forced tile included)
+// or the table's / the tuner's --, dropped when the op moves to another family.  MTV_WIN_PACKED=0, read here at every plan build (an A/B hook: one process can
+// hold a plan of each form), leaves the plan on the reads from ConvArgs::W.
+int attach_win_pack(mtv_ctx* c, ConvOp* op) {
+    ConvArgs& a = op->a;
+    a.Wwin = nullptr;
+    a.wwin_shape = 0;
+    const char* env = getenv("MTV_WIN_PACKED");
+    if ((env && atoi(env) == 0) || conv_family(op->t) != CONV_WIN || !conv_win_can_run(a, op->t, CONV_SLAB_ANY)) return MTV_OK;
+    const WinPack lay{op->t.NT, op->t.KS < 1 ? 1 : op->t.KS, a.Cmain, a.Cskip, a.N};
+    const float* p = c->wwin_for(a.W, a.ldw, lay);
+    if (!p) return fail(MTV_ERR_HIP, "packed 3x3 weight copy (k_conv_win): " + std::string(mtv_last_error()));
+    a.Wwin = p;
+    a.wwin_shape = 16 * lay.NT + lay.KS;
+    return MTV_OK;
+}
+
 void force_family_tile(const ConvArgs& a, ConvTile* t) {
     static const int win_xm = getenv("MTV_FORCE_WIN_XM") ? atoi(getenv("MTV_FORCE_WIN_XM")) != 0 : 0;      // (k_conv_win with the XCD-aware block order)
     for (ForcedTile* f : {&g_force_win, &g_force_pw, &g_force_b3, &g_force_lds}) {      // (in this order: the first family that can run the conv takes it)
@@ -1198,6 +1216,7 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
     for (auto& op : p->convs) {
         ConvArgs a = op->a;
         a.ddim = nullptr;       // the tuner times the conv itself, not the step hand-over
+        a.Wwin = nullptr;       // ... and its k_conv_win candidates on the legacy reads: the packed copy is made for the ONE tile that wins (below)
         auto run = [&](const ConvTile& tt) -> hipError_t { return op->tune_launch ? op->tune_launch(a, tt, s) : launch_conv(a, tt, s); };
         char key[176];
         snprintf(key, sizeof key, "B%d L%d/%d/%d N%d t%d C%d+%d gn%d f%d r%d s%d cm%d", a.B, a.Lout, a.Lsrc, a.Lskip, a.N, a.ntaps, a.Cmain, a.Cskip,
@@ -1335,6 +1354,7 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
         }
         op->t = it->second;
         p->ops[op->op_index].name = op->base_name + Builder::conv_tag(op->a, op->t);
+        if (const int rc = attach_win_pack(c, op.get())) return rc;
     }
     return MTV_OK;
 }
@@ -1575,6 +1595,7 @@ int mtv_load_weight(mtv_ctx* c, const char* key, const float* data, int ndim, co
     ++c->load_serial;
     for (auto& kv : c->w3) kv.second.dirty = true;      // (rebuilt before the next run: check_ready)
     for (auto& kv : c->wdeep) kv.second.dirty = true;
+    for (auto& kv : c->wwin) kv.second.dirty = true;
     return MTV_OK;
 }
 
@@ -1625,6 +1646,12 @@ int check_ready(mtv_ctx* c, int batch) {
     for (auto& kv : c->wdeep)
         if (kv.second.dirty) {
             HIPCHK(launch_deep_repack(kv.second.W, kv.second.ldw, kv.second.p, kv.second.lay, kv.second.NT, nullptr));
+            kv.second.dirty = false;
+            any = true;
+        }
+    for (auto& kv : c->wwin)
+        if (kv.second.dirty) {
+            HIPCHK(launch_win_repack(kv.second.W, kv.second.ldw, kv.second.p, kv.second.lay, nullptr));
             kv.second.dirty = false;
             any = true;
         }
@@ -2007,6 +2034,13 @@ int mtv_selftest_win(int res, int frames, int n_levels) {
             if (conv_win_selftest(lv[l].r, lv[l].t, up != 0, lv[l].L, src.L) != 0) return l + 1;
         }
     return 0;
+}
+
+int mtv_selftest_win_pack(int mt, int nt, int ks, int cmain, int cskip, int n) {
+    const WinPack p{nt, ks, cmain, cskip, n};
+    if (!conv_win_tile_exists(ConvTile{mt, nt, CONV_WIN, ks, 0}) || cmain <= 0 || cskip < 0 || n <= 0 || !win_pack_valid(p))
+        return fail(MTV_ERR_INVALID, "selftest_win_pack: no such tile, or a shape it cannot slice");
+    return win_pack_selftest(p);
 }
 
 int mtv_selftest_deep(int res, int frames, int n_levels) {

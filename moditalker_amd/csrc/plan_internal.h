@@ -207,6 +207,25 @@ struct mtv_ctx {
         }
         return it->second.p;
     }
+    // k_conv_win's packed copies of 3x3 conv matrices (ConvArgs::Wwin): one per (matrix, NT, KS) -- the tile an op finally runs on --, rebuilt after weight loads
+    struct WWinInfo { float* p; const float* W; int ldw; WinPack lay; bool dirty; };
+    std::map<std::string, WWinInfo> wwin;
+    size_t wwin_total_bytes = 0;
+    const float* wwin_for(const float* W, int ldw, const WinPack& lay) {
+        if (!win_pack_valid(lay) || lay.N > ldw) return nullptr;
+        char key[160];
+        snprintf(key, sizeof key, "%p %d %d %d %d %d %d", (const void*)W, ldw, lay.NT, lay.KS, lay.Cmain, lay.Cskip, lay.N);
+        auto it = wwin.find(key);
+        if (it == wwin.end()) {
+            void* p = nullptr;
+            if (dmalloc(&p, win_pack_floats(lay) * sizeof(float)) != MTV_OK) return nullptr;
+            it = wwin.emplace(key, WWinInfo{(float*)p, W, ldw, lay, true}).first;
+            wwin_total_bytes += win_pack_floats(lay) * sizeof(float);
+            // (tiles are chosen after check_ready's refresh: pack what the weight holds now; not loaded yet = packed again before the first run)
+            if (launch_win_repack(W, ldw, (float*)p, lay, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) return nullptr;
+        }
+        return it->second.p;
+    }
     const void* w3_for(const float* W, int K, int ld, unsigned long long* plane_out) {
         if (K & 7) return nullptr;
         auto it = w3.find(W);
@@ -320,4 +339,5 @@ constexpr long X3_MIN_ROWS = 1024;
 bool x3_wanted(long rows);                                  // plan.hip: offer this conv to the split-bf16 kernels?
 int check_ready(mtv_ctx* c, int batch);                     // (also refreshes the split-bf16 weight copies after a weight load)
 int ctx_init_common(mtv_ctx* c);
-void force_family_tile(const ConvArgs& a, ConvTile* t);    // MTV_FORCE_WIN / _PW / _B3 / _LDS and the mtv_debug_force_* testing aids
+int attach_win_pack(mtv_ctx* c, ConvOp* op);               // ConvArgs::Wwin for the k_conv_win tile an op runs on (MTV_WIN_PACKED=0: none)
+void force_family_tile(const ConvArgs& a, ConvTile* t);   // MTV_FORCE_WIN / _PW / _B3 / _LDS and the mtv_debug_force_* testing aids

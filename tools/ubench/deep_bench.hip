@@ -752,9 +752,19 @@ static void do_win(int nops, int r, int t, int C) {
         CK(hipMemcpy(sites, hs.data(), 192 * 8, hipMemcpyHostToDevice));
     }
     std::vector<float> ref;
-    auto run_tile = [&](ConvTile tile) {
-        if (tile.NW == 80 && !conv_win_eligible(ca[0], tile.MT, tile.NT)) return;
+    // packed != 0 (k_conv_win tiles only): every op reads its weights from the packed copy of its matrix for this tile (ConvArgs::Wwin; the product: attach_win_pack)
+    auto run_tile = [&](ConvTile tile, int packed = 0) {
+        for (int o = 0; o < nops; ++o) { ca[o].Wwin = nullptr; ca[o].wwin_shape = 0; }       // (a copy is one tile's: eligibility is asked without one)
+        if (tile.NW == 80 && !conv_win_eligible(ca[0], tile.MT, tile.NT, tile.KS)) return;
         if (tile.NW != 80 && conv_smem_bytes(ca[0], tile) > 120 * 1024) return;
+        std::vector<float*> dP;
+        for (int o = 0; o < nops && packed; ++o) {
+            const WinPack lay{tile.NT, tile.KS, C, 0, N};
+            dP.push_back(dnew<float>(win_pack_floats(lay)));
+            CK(launch_win_repack(dW[o], ldw, dP.back(), lay, s));
+            ca[o].Wwin = dP.back(); ca[o].wwin_shape = 16 * tile.NT + tile.KS;
+        }
+        CK(hipStreamSynchronize(s));
         CK(hipMemcpy(actA[0], x.data(), x.size() * 4, hipMemcpyHostToDevice));
         hipGraph_t gr; hipGraphExec_t ge;
         CK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -776,7 +786,8 @@ static void do_win(int nops, int r, int t, int C) {
         for (int i = 0; i < reps; ++i) CK(hipGraphLaunch(ge, s));
         CK(hipEventRecord(e1, s)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
-        printf("  tile %d,%d,%d,%d,%d  %7.2f us per op   (max|diff| to the first tile after %d ops %.2e)\n", tile.MT, tile.NT, tile.NW, tile.KS, tile.XM, ms * 1e3 / reps / nops, nops, worst);
+        printf("  tile %d,%d,%d,%d,%d%s  %7.2f us per op   (max|diff| to the first tile after %d ops %.2e)\n", tile.MT, tile.NT, tile.NW, tile.KS, tile.XM,
+               tile.NW == 80 ? (packed ? " packed" : " legacy") : "", ms * 1e3 / reps / nops, nops, worst);
 #ifdef MTV_DEEP_STAMP
         if (tile.NW == 80) {
             unsigned long long h[64];
@@ -793,9 +804,18 @@ static void do_win(int nops, int r, int t, int C) {
 #endif
         CK(hipGraphExecDestroy(ge));
         CK(hipGraphDestroy(gr));
+        for (float* p : dP) CK(hipFree(p));
     };
-    const ConvTile tiles[] = {{1, 4, 8, 1, 0}, {2, 4, 8, 1, 0}, {2, 2, 8, 1, 0}, {2, 4, 4, 1, 0}, {1, 2, 8, 1, 0}, {1, 4, 80, 1, 0}, {1, 2, 80, 1, 0}, {2, 2, 80, 1, 0}, {1, 2, 80, 1, 1}, {2, 2, 80, 1, 1}, {2, 4, 80, 1, 0}};
-    for (const ConvTile& tl : tiles) run_tile(tl);
+    const ConvTile tiles[] = {{1, 4, 8, 1, 0}, {2, 4, 8, 1, 0}, {2, 2, 8, 1, 0}, {2, 4, 4, 1, 0}, {1, 2, 8, 1, 0}, {1, 4, 80, 1, 0}, {1, 2, 80, 1, 0}, {2, 2, 80, 1, 0}, {1, 2, 80, 1, 1}, {2, 2, 80, 1, 1}, {2, 4, 80, 1, 0},
+                              {1, 2, 80, 2, 0}, {1, 4, 80, 2, 0}};
+    for (const ConvTile& tl : tiles) {
+        run_tile(tl);
+        if (tl.NW == 80) {                                    // legacy / packed interleaved, twice: the second pair shows what a repeat moves
+            run_tile(tl, 1);
+            run_tile(tl);
+            run_tile(tl, 1);
+        }
+    }
 }
 
 
