@@ -416,6 +416,50 @@ int mtv_hubert_profile(mtv_ctx* ctx, const float* wave, int n_samples, int batch
 int mtv_hubert_debug_keep(mtv_ctx* ctx, int keep);
 int mtv_hubert_debug_tap(mtv_ctx* ctx, const char* name, float* dst, int64_t cap, int* rows_out, int* channels_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Both ends of the MToV chunk loop (csrc/frames.hip): what MToV/sample.py:305-400 and MToV/tools/dataloader_sample.py:130-247 do on
+ * the host around the extracts, the sampler and the decode.  Three context-free calls: they launch on the current device into
+ * `stream`, all tensors are contiguous device pointers, every argument is checked before anything is launched.  All three are
+ * gathers (a thread computes whole output elements from clipped source coordinates; no input value takes part in a store address,
+ * no atomics).  Sides (res, canvas) are multiples of 4 up to 8192, batch and frames at most 4096; float tensors are 16-byte
+ * aligned, 8-bit outputs and integer tables 4-byte aligned.
+ * ------------------------------------------------------------------------------------------------ */
+/* resize_crop (MToV/tools/data_utils.py:73-98) and `x / 127.5 - 1` with the b t c -> b c t transpose (sample.py:323-326):
+ *   src [B, frames_in, 3, height, width] 8-bit, frames_in = frames or 1 (one frame repeated over `frames`: how x_ref is built)
+ *   mask_start [B, frames] int32 or NULL: source rows >= mask_start[b][t] (row numbers of the uncropped frame) read as 0, i.e.
+ *              _crop_lower_half (dataloader_sample.py:130-139) applied before the resize, the reference's order
+ *   out [B, 3, frames, res, res] fp32.
+ * Per output pixel: centre crop to the square S x S of the short side (half = (long - short) / 2 rounded down, for either
+ * orientation), bilinear resize with align_corners = False and no antialiasing in ATen's float arithmetic --
+ * scale = float(S) / res; src = scale * (dst + 0.5) - 0.5, below 0 -> 0; i0 = int(src); i1 = i0 + (i0 < S - 1); lambda1 = src - i0;
+ * lambda0 = 1 - lambda1; value = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d) without fused multiply-adds -- then
+ * value / 127.5 - 1, two roundings, in the form `division` names:
+ *   MTV_FRAMES_DIV_IEEE        an IEEE division: what torch computes for x / 127.5 - 1 on the host;
+ *   MTV_FRAMES_DIV_RECIPROCAL  value * fp32(1 / 127.5): what torch computes on a HIP device, where a division by a scalar becomes a
+ *                              multiplication by its reciprocal -- the form sample.py:318-326 gets, its tensors being on the device by
+ *                              then.  It differs from the division in the last bit for 111 of the 256 byte values.
+ * With height == width == res the weights are exactly 1 and 0 and the result is bit-equal to that form of byte / 127.5 - 1. */
+#define MTV_FRAMES_DIV_IEEE 0
+#define MTV_FRAMES_DIV_RECIPROCAL 1
+int mtv_frames_prep(const uint8_t* src, const int32_t* mask_start, float* out, int batch, int frames_in, int frames, int height,
+                    int width, int res, int division, void* stream);
+/* The landmark video (_change_np_img_size, dataloader_sample.py:153-179, in model range):
+ *   centres [B, frames, points, 2] int32 (x, y) disc centres on the canvas, any value (off-canvas parts clip); points <= 1024
+ *   half_width [2 * radius + 1] int32: row cy + dy of a disc spans cx - half_width[dy + radius] .. cx + half_width[dy + radius]
+ *              (negative: no pixel in that row); radius <= 31.  The caller states the scan-conversion rule (OpenCV's for cv2.circle).
+ *   out [B, 3, frames, canvas, canvas] fp32: +1 inside any disc, -1 outside, the three channels equal. */
+int mtv_frames_discs(const int32_t* centres, const int32_t* half_width, float* out, int batch, int frames, int points, int radius,
+                     int canvas, void* stream);
+/* Decoded frames to what the loop stores and chains (sample.py:385-398, 402, 349-360):
+ *   decoded [B * frames, 3, res, res] fp32, unclamped (mtv_ae_decode's output); s = (1 + min(max(v, -1), 1)) * 127.5 (a NaN reads as -1)
+ *   frames_u8 [B, frames, res, res, 3]: s truncated to 8 bits
+ *   last_u8 [B, res, res, 3] or NULL: the last frame of every clip, s rounded half to even (np.rint) and clipped to 0..255
+ *   next_ref [B, 3, frames, res, res] fp32 or NULL: last_u8 / 255 * 2 - 1 (IEEE division) repeated over the frames: the video
+ *            whose extract is the next chunk's image_cond.
+ * last_u8 and next_ref are requested together or not at all. */
+int mtv_frames_finish(const float* decoded, uint8_t* frames_u8, uint8_t* last_u8, float* next_ref, int batch, int frames, int res,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,9 @@ SYMBOLS = [
     ("mtv_hubert_profile", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(MtvOpTime), C.c_int, C.POINTER(C.c_int), _P]),
     ("mtv_hubert_debug_keep", C.c_int, [_P, C.c_int]),
     ("mtv_hubert_debug_tap", C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("mtv_frames_prep", C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    ("mtv_frames_discs", C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    ("mtv_frames_finish", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     ("mtv_selftest_geometry", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_deep", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_block", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -338,6 +338,9 @@ def audio_to_hubert(speech, model, save_path: Optional[str] = None) -> np.ndarra
 # ------------------------------------------------------------------------------------------------------------------
 # the chunk loop (sample.py:305-400)
 # ------------------------------------------------------------------------------------------------------------------
+_DIVISION_ON = {}          # device -> form of x / 127.5 - 1 that to_model_range takes there (MToVSampler._model_range_division)
+
+
 class MToVSampler:
     """diffusion_model: moditalker_amd.DDPM; first_stage_model / first_stage_model_ldmk: moditalker_amd.ViTAutoencoder
     (the reference loads two checkpoints of the same architecture, sample.py:206-218)."""
@@ -424,6 +427,127 @@ class MToVSampler:
                 chained[ldmk_srt + T] = self.chained_image_cond(fake, out_dir, ldmk_srt + T)
                 chained.pop(ldmk_srt - stride, None)  # (no longer reachable: keeps at most two latents alive)
             u8 = frames_to_uint8(fake)
+            results.append(u8)
+            if out_dir is not None:
+                save_frames(ldmk_srt, np.concatenate(list(u8), axis=2), os.path.join(out_dir, "frames"))
+        return results
+
+    # --------------------------------------------------------------------------------------------------------------
+    # the same loop with both ends on the device (moditalker_amd.frames, csrc/frames.hip): source frames go up as 8-bit,
+    # landmarks as integers, frames come down as 8-bit, the chained reference never leaves the GPU
+    # --------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def _model_range_division(self, dev) -> str:
+        """Which form of x / 127.5 - 1 `to_model_range` takes on `dev`, where `conditioning` evaluates it (sample.py:318-326 moves
+        the tensors to the device first, too): "ieee" or "reciprocal" (moditalker_amd.frames.prepare_frames).  Found by evaluating
+        it there on the 256 byte values, once per device."""
+        key = str(dev)
+        if key not in _DIVISION_ON:
+            x = torch.arange(256, dtype=torch.float32).reshape(1, 1, 1, 16, 16)
+            there = to_model_range(x.to(dev)).cpu()
+            forms = {"ieee": to_model_range(x),
+                     "reciprocal": (x * (torch.tensor(1.0) / 127.5) - 1).permute(0, 2, 1, 3, 4).contiguous()}
+            match = [k for k, v in forms.items() if torch.equal(v, there)]
+            if not match:
+                from ._lib import MtvError
+                raise MtvError(f"x / 127.5 - 1 on {dev} is neither an IEEE division nor a multiplication by the fp32 reciprocal: "
+                               "k_frames_prep has no form for it; pass division= explicitly")
+            _DIVISION_ON[key] = match[0]
+        return _DIVISION_ON[key]
+
+    @torch.no_grad()
+    def conditioning_device(self, ref_u8, vid_u8, landmarks, y33, WH: Optional[int] = None, division: Optional[str] = None):
+        """`conditioning` from what the reference's loader starts with (dataloader_sample.py:181-247) instead of four float videos:
+          ref_u8     uint8 [B, 1, 3, h, w] (the identity's first frame, repeated over T on the device) or [B, T, 3, h, w]
+          vid_u8     uint8 [B, T, 3, h, w] source frames of any size (centre crop + bilinear resize happen on the device)
+          landmarks  [B, T, 68, 2] image-sized or [B, T, 68, 3] normalised, as `landmarks_to_images` takes them per clip
+          y33        [B, T] landmark 33's y in source rows: rows from int(y) downwards are zeroed in masked_x (`crop_lower_half`)
+          WH         the landmarks' image size, default the source width (dataloader_sample.py:224-225)
+          division   the form of x / 127.5 - 1 (prepare_frames): default the one `to_model_range` takes on the device, which is
+                     what `conditioning` computes; "ieee" is the host's
+        Tensors may be on the host (they are uploaded as they are, 8-bit) or on the device.  Returns the dict `conditioning` returns.
+        The loader's half-length branch (dataloader_sample.py:234-239: a clip of nframes / 2 frames is padded with zero frames in
+        front) is not built: clips have T frames."""
+        from . import frames as F
+        dev = next(self.ae.parameters()).device
+        T, res = self.ae.s, self.ae.res
+        if self.ae_ldmk.res != F.CANVAS:
+            raise ValueError(f"the landmark canvas is {F.CANVAS} x {F.CANVAS} (dataloader_sample.py:163); the landmark autoencoder takes {self.ae_ldmk.res}")
+        vid_u8, ref_u8 = torch.as_tensor(vid_u8), torch.as_tensor(ref_u8)
+        if vid_u8.dim() != 5 or vid_u8.shape[1] != T:
+            raise ValueError(f"vid_u8 must be [B, {T}, 3, h, w]; got {tuple(vid_u8.shape)}")
+        B, h, w = vid_u8.shape[0], vid_u8.shape[3], vid_u8.shape[4]
+        if ref_u8.dim() != 5 or ref_u8.shape[0] != B or tuple(ref_u8.shape[2:]) != (3, h, w):
+            raise ValueError(f"ref_u8 must be [{B}, 1 or {T}, 3, {h}, {w}]; got {tuple(ref_u8.shape)}")
+        centres = F.disc_centres(landmarks, w if WH is None else WH)
+        start = F.mask_start(y33, h)
+        if centres.ndim != 4 or centres.shape[:2] != (B, T) or start.shape != (B, T):
+            raise ValueError(f"landmarks must be [{B}, {T}, points, 2 or 3] and y33 [{B}, {T}]; got {centres.shape[:-1]} and {start.shape}")
+        vid_u8, ref_u8 = vid_u8.to(dev).contiguous(), ref_u8.to(dev).contiguous()
+        division = self._model_range_division(dev) if division is None else division
+        x = F.prepare_frames(vid_u8, res, division=division)
+        x_ref = F.prepare_frames(ref_u8, res, frames=T, division=division)
+        masked_x = F.prepare_frames(vid_u8, res, mask_start=torch.from_numpy(start).to(dev), division=division)
+        x_l = F.landmark_frames(torch.from_numpy(np.ascontiguousarray(centres)).to(dev))
+        z_ = self.ae.extract(x)
+        image_cond_ = self.ae.extract(x_ref)
+        z_l = self.ae_ldmk.extract(x_l)
+        masked_z = self.ae.extract(masked_x)
+        return dict(z_=z_, image_cond_=image_cond_, image_cond=image_cond_[:, :, 0:self.n_xy],
+                    c=torch.cat([z_l, masked_z], dim=1))
+
+    @torch.no_grad()
+    def sample_chunk_device(self, cond: dict, image_cond: Optional[torch.Tensor] = None, x_noisy_start: bool = False,
+                            refvid_noisy_start: bool = False, ratio_: Optional[float] = None, fix_noise: bool = False, noise=None,
+                            want_next_ref: bool = False):
+        """`sample_chunk` without the host: -> (z [B,4,L], frames_u8 uint8 [B,T,H,W,3], last_u8 uint8 [B,H,W,3], next_ref
+        [B,3,T,H,W]), all on the device.  frames_u8 is frames_to_uint8 of sample_chunk's frames; last_u8 / next_ref
+        (None unless want_next_ref) are last_frame_to_uint8 and reference_from_uint8 of them."""
+        from . import frames as F
+        k = cond["c"].shape[0]
+        noised_start = None
+        if x_noisy_start:
+            noised_start = cond["image_cond_"].float()
+        elif refvid_noisy_start:
+            noised_start = cond["z_"].float()
+        z = self.dm.sample(batch_size=k, cond=cond["c"].float(),
+                           image_cond=(image_cond if image_cond is not None else cond["image_cond"]).float(),
+                           noised_start=noised_start, ratio_=ratio_, fix_noise=fix_noise, noise=noise)
+        frames_u8, last_u8, next_ref = F.finish_frames(self.ae.decode_from_sample(z).float().contiguous(), k, want_next_ref=want_next_ref)
+        return z, frames_u8, last_u8, next_ref
+
+    @torch.no_grad()
+    def run_identity_device(self, chunks, use_last_as_reference: bool = False, out_dir: Optional[str] = None,
+                            noise_per_chunk: Optional[Sequence] = None, overlap: bool = False, num_frames: Optional[int] = None,
+                            WH: Optional[int] = None, division: Optional[str] = None, **sample_kw):
+        """`run_identity` on conditioning_device / sample_chunk_device: chunks yield (ref_u8, vid_u8, landmarks, y33) (see
+        conditioning_device).  Same keyword arguments (`WH` and `division` are passed on to conditioning_device), same returned list of uint8 arrays
+        [B, T, H, W, 3], same files under out_dir: frames/NNNN.png, and with `use_last_as_reference` references/<n>/<idx>.png from
+        last_u8.  The chained image_cond is the extract of next_ref, which never passes through the host (the PNG is written, not
+        read back: it holds exactly the bytes next_ref was made from).  The only downloads are the 8-bit frames."""
+        results = []
+        T = self.ae.s
+        stride = T // 2 if overlap else T
+        chained = {}
+        for it, (ref_u8, vid_u8, landmarks, y33) in enumerate(chunks):
+            ldmk_srt = it * stride
+            if num_frames is not None and num_frames < ldmk_srt:
+                break
+            cond = self.conditioning_device(ref_u8, vid_u8, landmarks, y33, WH=WH, division=division)
+            nz = noise_per_chunk[it] if noise_per_chunk is not None else None
+            z, frames_u8, last_u8, next_ref = self.sample_chunk_device(
+                cond, image_cond=chained.get(ldmk_srt) if use_last_as_reference else None, noise=nz,
+                want_next_ref=use_last_as_reference, **sample_kw)
+            if use_last_as_reference:
+                chained[ldmk_srt + T] = self.ae.extract(next_ref)[:, :, 0:self.n_xy]
+                chained.pop(ldmk_srt - stride, None)
+                if out_dir is not None:
+                    from PIL import Image
+                    folder = os.path.join(out_dir, "references", str(ldmk_srt + T))
+                    os.makedirs(folder, exist_ok=True)
+                    for idx, img in enumerate(last_u8.cpu().numpy()):
+                        Image.fromarray(img, "RGB").save(os.path.join(folder, f"{idx}.png"))
+            u8 = frames_u8.cpu().numpy()
             results.append(u8)
             if out_dir is not None:
                 save_frames(ldmk_srt, np.concatenate(list(u8), axis=2), os.path.join(out_dir, "frames"))
