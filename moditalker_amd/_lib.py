@@ -90,9 +90,9 @@ class MtvOpTime(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("ms", C.c_float), ("flops", C.c_double), ("bytes", C.c_double)]
 
 
-# every symbol include/mtv_hip.h declares: (name, restype, argtypes)
+# every symbol the two headers declare: (name, restype, argtypes)
 _P = C.c_void_p
-SYMBOLS = [
+PRODUCT_SYMBOLS = [        # include/mtv_hip.h
     ("mtv_last_error", C.c_char_p, []),
     ("mtv_version", C.c_int, []),
     ("mtv_create", C.c_int, [C.POINTER(MtvConfig), C.POINTER(_P)]),
@@ -103,22 +103,10 @@ SYMBOLS = [
     ("mtv_weights_missing", C.c_int, [_P]),
     ("mtv_forward", C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P]),
     ("mtv_ddim_sample", C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.POINTER(MtvDdimStep), C.c_int, C.c_int, _P]),
-    ("mtv_debug_tap", C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mtv_get_work", C.c_int, [_P, C.POINTER(MtvWork)]),
     ("mtv_set_eager", C.c_int, [_P, C.c_int]),
     ("mtv_profile_forward", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(MtvOpTime), C.c_int, C.POINTER(C.c_int), _P]),
     ("mtv_profile_step", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(MtvOpTime), C.c_int, C.POINTER(C.c_int), _P]),
-    ("mtv_debug_stamps", C.c_int, [_P, C.c_int, C.c_char_p, _P]),
-    ("mtv_debug_force_lds", C.c_int, [C.c_int, C.c_int]),
-    ("mtv_debug_force_win", C.c_int, [C.c_int, C.c_int]),
-    ("mtv_debug_force_win_ks", C.c_int, [C.c_int, C.c_int, C.c_int]),
-    ("mtv_debug_force_pw", C.c_int, [C.c_int, C.c_int]),
-    ("mtv_debug_force_pw_waves", C.c_int, [C.c_int, C.c_int, C.c_int]),
-    ("mtv_debug_force_b3", C.c_int, [C.c_int, C.c_int, C.c_int]),
-    ("mtv_debug_attention_qb", C.c_int, [C.c_int]),
-    ("mtv_debug_deep", C.c_int, [C.c_int]),
-    ("mtv_debug_deep_options", C.c_int, [C.c_int]),
-    ("mtv_debug_deep_attn_form", C.c_int, [C.c_int]),
     ("mtv_ae_create", C.c_int, [C.POINTER(MtvAeConfig), C.POINTER(_P)]),
     ("mtv_ae_destroy", C.c_int, [_P]),
     ("mtv_ae_set_rotary", C.c_int, [_P, _P, _P]),
@@ -146,22 +134,38 @@ SYMBOLS = [
     ("mtv_hubert_forward", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     ("mtv_hubert_num_launches", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     ("mtv_hubert_profile", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(MtvOpTime), C.c_int, C.POINTER(C.c_int), _P]),
-    ("mtv_hubert_debug_keep", C.c_int, [_P, C.c_int]),
-    ("mtv_hubert_debug_tap", C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mtv_frames_prep", C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("mtv_frames_discs", C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("mtv_frames_finish", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    ("mtv_check_fault", C.c_int, [_P]),
+    ("mtv_resident_cus", C.c_int, [_P]),
+]
+DEBUG_SYMBOLS = [          # include/mtv_hip_debug.h: testing aids, self-tests, diagnostics
+    ("mtv_debug_options_dump", C.c_int, [_P, C.c_char_p, C.c_int]),
+    ("mtv_debug_tap", C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("mtv_debug_stamps", C.c_int, [_P, C.c_int, C.c_char_p, _P]),
+    ("mtv_debug_force_lds", C.c_int, [C.c_int, C.c_int]),
+    ("mtv_debug_force_win", C.c_int, [C.c_int, C.c_int]),
+    ("mtv_debug_force_win_ks", C.c_int, [C.c_int, C.c_int, C.c_int]),
+    ("mtv_debug_force_pw", C.c_int, [C.c_int, C.c_int]),
+    ("mtv_debug_force_pw_waves", C.c_int, [C.c_int, C.c_int, C.c_int]),
+    ("mtv_debug_force_b3", C.c_int, [C.c_int, C.c_int, C.c_int]),
+    ("mtv_debug_attention_qb", C.c_int, [C.c_int]),
+    ("mtv_debug_deep", C.c_int, [C.c_int]),
+    ("mtv_debug_deep_options", C.c_int, [C.c_int]),
+    ("mtv_debug_deep_attn_form", C.c_int, [C.c_int]),
+    ("mtv_hubert_debug_keep", C.c_int, [_P, C.c_int]),
+    ("mtv_hubert_debug_tap", C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mtv_selftest_geometry", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_deep", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_block", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_win", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("mtv_selftest_win_pack", C.c_int, [C.c_int] * 6),
     ("mtv_debug_gather_index", C.c_int, [C.c_int] * 6),
-    ("mtv_check_fault", C.c_int, [_P]),
-    ("mtv_resident_cus", C.c_int, [_P]),
     ("mtv_debug_resident_cus", C.c_int, [C.c_int]),
     ("mtv_debug_arm_fault", C.c_int, [_P]),
 ]
+SYMBOLS = PRODUCT_SYMBOLS + DEBUG_SYMBOLS
 
 _lib: Optional[C.CDLL] = None
 

@@ -324,11 +324,12 @@ struct AeBuilder {
         a.res = res;
         a.gather = gather;
         a.stat_cstride = 0;
-        if (x3_wanted((long)a.B * rows)) a.W3 = c->w3_for(W, K, ld, &a.w3_plane);      // split-bf16 weight copy for k_conv_x3
+        if (x3_wanted(c->opt, (long)a.B * rows)) a.W3 = c->w3_for(W, K, ld, &a.w3_plane);      // split-bf16 weight copy for k_conv_x3
         auto op = std::make_shared<ConvOp>();
         op->a = a;
-        op->t = conv_pick_tile(a.B, rows, N, K / 16, K, false);
-        force_family_tile(a, &op->t);
+        const PlanOptions* o = &c->opt;           // (the op closures hold a pointer to the context's settings)
+        op->t = conv_pick_tile(*o, a.B, rows, N, K / 16, K, false);
+        force_family_tile(*o, a, &op->t);
         op->base_name = "gemm:" + name;
         op->op_index = (int)plan->ops.size();
         plan->convs.push_back(op);
@@ -339,24 +340,23 @@ struct AeBuilder {
         if (geglu_h) {       // the tuner times each candidate as the plan would run it: fused pair, or k_geglu + the GEMM
             float* gl = const_cast<float*>(in);
             const long ntok_all = (long)a.B * rows;
-            op->tune_launch = [geglu_h, gl, ntok_all, K](const ConvArgs& ta, ConvTile tt, hipStream_t s) -> hipError_t {
+            op->tune_launch = [geglu_h, gl, ntok_all, K, o](const ConvArgs& ta, ConvTile tt, hipStream_t s) -> hipError_t {
                 ConvOp probe;
                 probe.a = ta;
                 probe.t = tt;
-                if (x3_fused_geglu(probe)) return launch_conv_x3_geglu(ta, tt, geglu_h, s);
+                if (x3_fused_geglu(probe, *o)) return launch_conv_x3_geglu(ta, tt, geglu_h, s);
                 hipError_t e = launch_geglu(geglu_h, gl, ntok_all, K, 0, s);
-                return e != hipSuccess ? e : launch_conv(ta, tt, s);
+                return e != hipSuccess ? e : launch_conv(ta, tt, *o, s);
             };
         }
         if (geglu_h)
-            push(op->base_name + tag, [op, geglu_h](hipStream_t s) { return x3_fused_geglu(*op) ? launch_conv_x3_geglu(op->a, op->t, geglu_h, s) : launch_conv(op->a, op->t, s); }, flops, bytes);
+            push(op->base_name + tag, [op, geglu_h, o](hipStream_t s) { return x3_fused_geglu(*op, *o) ? launch_conv_x3_geglu(op->a, op->t, geglu_h, s) : launch_conv(op->a, op->t, *o, s); }, flops, bytes);
         else
-            push(op->base_name + tag, [op](hipStream_t s) { return launch_conv(op->a, op->t, s); }, flops, bytes);
+            push(op->base_name + tag, [op, o](hipStream_t s) { return launch_conv(op->a, op->t, *o, s); }, flops, bytes);
         return op;
     }
-    static bool x3_fused_geglu(const ConvOp& op) {
-        static const bool off = getenv("MTV_AE_NO_GEGLU_FUSION") != nullptr;
-        return !off && conv_family(op.t) == CONV_X3 && !op.a.gather && conv_x3_eligible(op.a) && op.a.x3 != nullptr;
+    static bool x3_fused_geglu(const ConvOp& op, const PlanOptions& o) {
+        return !o.ae_no_geglu_fusion && conv_family(op.t) == CONV_X3 && !op.a.gather && conv_x3_eligible(op.a) && op.a.x3 != nullptr;
     }
 
     float* lin_w(const std::string& key, int N, int K, int* ld_out) {        // Linear [N][K] -> [K][ld]
@@ -394,7 +394,7 @@ struct AeBuilder {
         t.scale = 1.0f / std::sqrt(std::sqrt((float)d));       // q * d^-1/2 (vit_modules.py:125) split evenly over q and k
         t.seg_uniform = period;
         const double aflops = 4.0 * B * H * (double)D.ntok * period * d;
-        push("attn:" + nm, [t](hipStream_t s) { return launch_attention(t, s); }, aflops, 16.0 * ntok * inner);
+        push("attn:" + nm, [t, o = &c->opt](hipStream_t s) { return launch_attention(t, *o, s); }, aflops, 16.0 * ntok * inner);
         int ldo;
         float* Wo = lin_w(key + "fn.to_out.0.weight", C, inner, &ldo);
         const float* bo = vec(key + "fn.to_out.0.bias", C);
@@ -420,7 +420,7 @@ struct AeBuilder {
             gemm(nm + ".ff1", ln, C, W1, ld1, b1, 8 * C, hid, D.ntok);
             const int half = 4 * C;
             auto ff2 = std::make_shared<std::shared_ptr<ConvOp>>();      // (the GEGLU launch comes first in the plan, the GEMM it may fold into second)
-            push("geglu:" + nm, [=](hipStream_t s) { return *ff2 && x3_fused_geglu(**ff2) ? hipSuccess : launch_geglu(hid, gl, ntok, half, 0, s); }, 0.0, 4.0 * ntok * 12 * C);
+            push("geglu:" + nm, [=, o = &c->opt](hipStream_t s) { return *ff2 && x3_fused_geglu(**ff2, *o) ? hipSuccess : launch_geglu(hid, gl, ntok, half, 0, s); }, 0.0, 4.0 * ntok * 12 * C);
             float* W2 = lin_w(p + "2.fn.net.3.weight", C, 4 * C, &ld2);
             const float* b2 = vec(p + "2.fn.net.3.bias", C);
             *ff2 = gemm(nm + ".ff2", gl, 4 * C, W2, ld2, b2, C, x, D.ntok, x, nullptr, -1, hid);
@@ -448,7 +448,7 @@ struct AeBuilder {
             t.qkv = qkv; t.out = att; t.B = 1; t.L = (int)ntok; t.C = inner; t.H = H;
             t.scale = 1.0f / std::sqrt(std::sqrt((float)d));   // dots * d^-1/2 (autoencoder_vit.py:55)
             t.seg_uniform = n1;
-            push("attn:" + nm, [t](hipStream_t s) { return launch_attention(t, s); }, 4.0 * H * (double)ntok * n1 * d, 16.0 * ntok * inner);
+            push("attn:" + nm, [t, o = &c->opt](hipStream_t s) { return launch_attention(t, *o, s); }, 4.0 * H * (double)ntok * n1 * d, 16.0 * ntok * inner);
             int ldo, ld1, ld2;
             float* Wo = lin_w(p + "0.fn.to_out.0.weight", C, inner, &ldo);
             const float* bo = vec(p + "0.fn.to_out.0.bias", C);

@@ -791,10 +791,6 @@ __global__ __launch_bounds__(NW * 64) void k_conv(const ConvArgs a) {
             double* dst = a.stat[t].sums + (size_t)(blockIdx.x & (STAT_COPIES - 1)) * a.stat_cstride + (((size_t)b * 3 + sgi) * 32 + g) * 2;
             atomicAdd(dst, s);
             atomicAdd(dst + 1, ss);
-            if (a.dbg_stat_dup) {
-                atomicAdd(dst + a.dbg_stat_dup, s);
-                atomicAdd(dst + a.dbg_stat_dup + 1, ss);
-            }
         }
     }
     MTV_STAMP(6);
@@ -1203,27 +1199,14 @@ static hipError_t launch_conv_lds_t(const ConvArgs& a0, hipStream_t s) {
     return hipGetLastError();
 }
 
-ConvTile conv_pick_tile(int B, int Lout, int N, int nchunks, int Cmain, bool has_gn) {
-    static int forced[4] = {-1, 0, 0, 0};   // tuning aid: MTV_FORCE_TILE="MT,NT,NW,KS"
-    if (forced[0] == -1) {
-        forced[0] = 0;
-        if (const char* e = getenv("MTV_FORCE_TILE")) {
-            int a = 0, b = 0, c = 0, d = 1;
-            if (sscanf(e, "%d,%d,%d,%d", &a, &b, &c, &d) >= 3) { forced[0] = a; forced[1] = b; forced[2] = c; forced[3] = d < 1 ? 1 : d; }
-        }
-    }
-    if (forced[0] > 0) {
-        ConvTile t{forced[0], forced[1], forced[2], forced[3], 0};
+ConvTile conv_pick_tile(const PlanOptions& o, int B, int Lout, int N, int nchunks, int Cmain, bool has_gn) {
+    if (o.force_tile[0] > 0) {              // tuning aid: MTV_FORCE_TILE="MT,NT,NW,KS"
+        ConvTile t{o.force_tile[0], o.force_tile[1], o.force_tile[2], o.force_tile[3], 0};
         while (t.NW * t.KS > nchunks && t.KS > 1) t.KS /= 2;
         while (t.NW * t.KS > nchunks && t.NW > 1) t.NW /= 2;
         return t;
     }
-    static double lat_us = -1.0, fin_us = 3.0;
-    if (lat_us < 0) {
-        lat_us = 0.7;
-        if (const char* e = getenv("MTV_LAT_US")) lat_us = atof(e);
-        if (const char* e = getenv("MTV_FIN_US")) fin_us = atof(e);
-    }
+    constexpr double lat_us = 0.7, fin_us = 3.0;
     static const int cand[][2] = {{4, 4}, {2, 4}, {1, 4}, {2, 2}, {1, 2}, {1, 1}};
     const int ntaps_guess = 9;
     ConvTile best{1, 1, 1, 1, 0};
@@ -1383,13 +1366,8 @@ hipError_t conv_init_attrs() {
     return conv_x3_init_attrs();
 }
 
-hipError_t launch_conv(const ConvArgs& a0, ConvTile t, hipStream_t s) {
+hipError_t launch_conv(const ConvArgs& a0, ConvTile t, const PlanOptions& o, hipStream_t s) {
     ConvArgs a = a0;
-    // timing experiment (results unchanged): MTV_DEBUG_STATDUP=1 makes every workgroup issue its GroupNorm-statistics atomics a
-    // SECOND time, into the other step parity's arena (unused during this step, zeroed by this step's head conv): the step
-    // time it adds is what the real ones cost
-    static const bool stat_dup = getenv("MTV_DEBUG_STATDUP") != nullptr;
-    if (!stat_dup) a.dbg_stat_dup = 0;
     a.KS = t.KS;
     a.xmap = t.XM;
     if (a.KS > 1 && (!a.slab || !a.tickets || (a.N & 3))) return hipErrorInvalidValue;
@@ -1401,14 +1379,14 @@ hipError_t launch_conv(const ConvArgs& a0, ConvTile t, hipStream_t s) {
     // A tile of one of the special kernels that this conv cannot run on after all (statistics targets are attached after a plan's op is
     // created, so a tile forced at that point can turn out ineligible) gives way to the analytic k_conv tile, unsliced.
     if (conv_family(t) != CONV_PLAIN && !conv_tile_runs(a, t, CONV_SLAB_ANY)) {
-        t = conv_pick_tile(a.B, a.Lout, a.N, a.ntaps * (a.Cmain / 16) + a.Cskip / 16, a.Cmain, a.gn.sums != nullptr);
+        t = conv_pick_tile(o, a.B, a.Lout, a.N, a.ntaps * (a.Cmain / 16) + a.Cskip / 16, a.Cmain, a.gn.sums != nullptr);
         t.KS = 1;
         a.KS = 1;
         a.xmap = t.XM;
     }
     switch (conv_family(t)) {
-        case CONV_WIN: return launch_conv_win(a, t, s);
-        case CONV_PW: return launch_conv_pw(a, t, s);
+        case CONV_WIN: return launch_conv_win(a, t, o, s);
+        case CONV_PW: return launch_conv_pw(a, t, o, s);
         case CONV_X3: return launch_conv_x3(a, t, s);       // (elementwise pass + gathering GEMM)
         case CONV_LDS:
             if (t.MT == 4 && t.NT == 4) return launch_conv_lds_t<4, 4>(a, s);

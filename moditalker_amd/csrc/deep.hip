@@ -2027,7 +2027,7 @@ static hipError_t deep_launch_t(const DeepArgs& a, size_t smem, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_deep_conv(const DeepArgs& a0, DeepTile t, hipStream_t s) {
+hipError_t launch_deep_conv(const DeepArgs& a0, DeepTile t, const PlanOptions& o, hipStream_t s) {
     DeepArgs a = a0;
     if (a.KS < 1 || (a.KS & (a.KS - 1)) || a.KS > 8 || (a.nrg != 1 && a.nrg != 2)) return hipErrorInvalidValue;
     if (a.CSm < 16 || (a.CSm & (a.CSm - 1)) || a.CSm > 512 || a.CSm * a.KS != a.Cmain) return hipErrorInvalidValue;
@@ -2048,12 +2048,9 @@ hipError_t launch_deep_conv(const DeepArgs& a0, DeepTile t, hipStream_t s) {
     a.inv_nslots = 1.0f / (float)a.nslots;
     a.xm = 0;
     a.xm_jbits = 0;
-    {
-        static const int env_xm = getenv("MTV_DEEP_XM") ? atoi(getenv("MTV_DEEP_XM")) : 1;       // (A/B hook: 0 = the plain order everywhere)
-        if (env_xm && a.B == 1 && a.nrg == 2 && a.KS <= 8 && a.tiles_n % (8 >> a.ks_shift) == 0) {
-            a.xm = 1;
-            a.xm_jbits = 3 - a.ks_shift;
-        }
+    if (o.deep_xm && a.B == 1 && a.nrg == 2 && a.KS <= 8 && a.tiles_n % (8 >> a.ks_shift) == 0) {       // (MTV_DEEP_XM=0: the plain order everywhere)
+        a.xm = 1;
+        a.xm_jbits = 3 - a.ks_shift;
     }
     a.inv_r = 1.0f / (float)a.r;
     a.inv_rs = 0.f;
@@ -2130,7 +2127,7 @@ static size_t deep_attn_smem(const DeepAttnArgs& a, int D, bool with_wt = false)
     return (size_t)(kos + D * VSTR + QR * KSTR + QR * AS + wt + 8 * 16 * 2 + fsc) * 4;
 }
 
-bool deep_attn_configure(DeepAttnArgs& a) {
+bool deep_attn_configure(DeepAttnArgs& a, const PlanOptions& o) {
     if (a.H < 1 || a.C % a.H || a.L < 1 || a.L > 128 || (a.C & 15)) return false;
     const int d = a.C / a.H;
     if (d != 16 && d != 32 && d != 64 && d != 128) return false;
@@ -2138,8 +2135,7 @@ bool deep_attn_configure(DeepAttnArgs& a) {
     // round 6: ONE query tile per workgroup x 8 key parts, proj slices up to 64 columns -- at [128 x 512] 8 query groups x 4 head groups x 8 column groups = the same
     // 256 workgroups, each recomputing half the attention (1.9482 -> 1.9385 ms per step same-box, profiles/r06_deep_attn_query_tile_ab.txt).  MTV_DEEP_ATTN_QT=2: round 4's
     // 2 query tiles x 4 key parts, 16- / 32-column slices
-    static const int env_qt = getenv("MTV_DEEP_ATTN_QT") ? atoi(getenv("MTV_DEEP_ATTN_QT")) : 1;
-    a.QT = env_qt == 2 ? 2 : 1;
+    a.QT = o.deep_attn_qt == 2 ? 2 : 1;
     if (d == 128 && a.QT != 1) return false;                 // 128-wide heads: one Q quad per thread means one query tile
     a.nqg = (a.L + 16 * a.QT - 1) / (16 * a.QT);
     // ONE head per workgroup, 128-column proj slices from the packed matrix (HPW = 1, NC = 128; QT = 1 only): at [128 x 512] d = 64 8 query groups x 8 head groups x 4
@@ -2147,15 +2143,13 @@ bool deep_attn_configure(DeepAttnArgs& a) {
     // 8; every wave owns one 16-column proj tile over the whole K slice.  Twice the output slabs (H of them) for the consumers to add.  The rule takes it where the step
     // was measured with it: 128-token blocks of 64-wide heads whose workgroups are all resident together (profiles/r07_deep_attn_heads.md).
     // MTV_DEEP_ATTN_HPW=2 (or form 2): never; form 1: wherever the form exists.
-    static const int env_hpw = getenv("MTV_DEEP_ATTN_HPW") ? atoi(getenv("MTV_DEEP_ATTN_HPW")) : 0;
-    const int form = a.form ? a.form : (env_hpw == 2 ? 2 : 0);
-    if (form != 2 && a.QT == 1 && a.Wpk && a.C % 128 == 0 && a.H <= 8 && !(a.H & (a.H - 1))) {
+    if (a.form != 2 && a.QT == 1 && a.Wpk && a.C % 128 == 0 && a.H <= 8 && !(a.H & (a.H - 1))) {
         a.HPW = 1; a.NC = 128; a.nhg = a.H; a.ncg = a.C / 128;
         const long wgs = (long)a.B * a.nqg * a.nhg * a.ncg;
         // 128-wide heads are one head per workgroup in any form (hpw d <= 128): the 128-column slice halves the workgroups that recompute a (head, query tile) against
         // 64 columns, at the same 8 slabs -- taken wherever it still fills half the chip (long-video model: 512 workgroups at 128 tokens, 128 at 32)
         const bool rule = d == 128 ? wgs >= 128 : (d == 64 && a.L > 112 && a.H == 8 && wgs >= 128 && wgs <= 256);
-        if ((form == 1 || rule) && deep_attn_smem(a, d) <= 160 * 1024) return true;
+        if ((a.form == 1 || rule) && deep_attn_smem(a, d) <= 160 * 1024) return true;
     }
     // head group = K slice of the projection = an output slab: as few slabs as the grid allows (consumers re-read every slab)
     for (int hpw : {8, 4, 2, 1}) {
@@ -2346,14 +2340,6 @@ static hipError_t conv_win_launch_t(const ConvArgs& a0, int xm, int KS, hipStrea
     a.tiles_per_b = tiles;
     a.tiles_n = tiles_n;
     a.Bt = a.B * tiles;
-    {
-        static const int env_rb = getenv("MTV_ROW_BLOCKED") ? atoi(getenv("MTV_ROW_BLOCKED")) : 0;       // (A/B hook)
-        if (env_rb && a.xmap == 0 && a.Bt % 8 == 0) {
-            a.xmap = 3;
-            a.Sx = a.Bt / 8;
-            a.inv_Sx = 1.0f / (float)a.Sx;
-        }
-    }
     a.inv_tiles_per_b = 1.0f / (float)tiles;
     a.inv_Bt = 1.0f / (float)a.Bt;
     a.cps_q = a.Cskip / KS;                                  // skip / tapped channels of a K slice; the kernel's chunk walk is per slice:
@@ -2370,9 +2356,8 @@ static hipError_t conv_win_launch_t(const ConvArgs& a0, int xm, int KS, hipStrea
     hipLaunchKernelGGL((k_conv_win<MT, NT, PK>), dim3((unsigned)(a.Bt * tiles_n * KS)), dim3(DEEP_NTH), smem, s, a);
     return hipGetLastError();
 }
-hipError_t launch_conv_win(const ConvArgs& a, ConvTile t, hipStream_t s) {
-    static const int env_xm = getenv("MTV_WIN_XM") ? atoi(getenv("MTV_WIN_XM")) : -1;       // (A/B hook: block order of every k_conv_win launch)
-    if (env_xm >= 0) t.XM = env_xm;
+hipError_t launch_conv_win(const ConvArgs& a, ConvTile t, const PlanOptions& o, hipStream_t s) {
+    if (o.win_xm >= 0) t.XM = o.win_xm;                      // (MTV_WIN_XM, A/B hook: block order of every k_conv_win launch)
     const int KS = t.KS < 1 ? 1 : t.KS;
     if (a.Wwin) {                                            // (conv_win_eligible: the copy is this tile's)
         if (t.MT == 1 && t.NT == 4) return conv_win_launch_t<1, 4, true>(a, t.XM, KS, s);
@@ -2433,23 +2418,14 @@ static hipError_t conv_pw_launch_t(const ConvArgs& a0, int xm, hipStream_t s) {
     a.tiles_per_b = tiles;
     a.tiles_n = groups;
     a.Bt = a.B * tiles;
-    {
-        static const int env_rb = getenv("MTV_ROW_BLOCKED") ? atoi(getenv("MTV_ROW_BLOCKED")) : 0;       // (A/B hook)
-        if (env_rb && a.xmap == 0 && a.Bt % 8 == 0) {
-            a.xmap = 3;
-            a.Sx = a.Bt / 8;
-            a.inv_Sx = 1.0f / (float)a.Sx;
-        }
-    }
     a.inv_tiles_per_b = 1.0f / (float)tiles;
     a.inv_Bt = 1.0f / (float)a.Bt;
     if ((long)a.Bt * groups >= (1L << 21)) return hipErrorInvalidValue;
     hipLaunchKernelGGL((k_conv_pw<MT, NTW, NWA>), dim3((unsigned)(a.Bt * groups)), dim3(DEEP_NTH), conv_pw_layout(a, MT, NTW, NWA), s, a);
     return hipGetLastError();
 }
-hipError_t launch_conv_pw(const ConvArgs& a, ConvTile t, hipStream_t s) {
-    static const int env_xm = getenv("MTV_PW_XM") ? atoi(getenv("MTV_PW_XM")) : -1;         // (A/B hook: block order of every k_conv_pw launch)
-    int xm = env_xm >= 0 ? env_xm : t.XM;
+hipError_t launch_conv_pw(const ConvArgs& a, ConvTile t, const PlanOptions& o, hipStream_t s) {
+    int xm = o.pw_xm >= 0 ? o.pw_xm : t.XM;                 // (MTV_PW_XM, A/B hook: block order of every k_conv_pw launch)
     if (xm == 2) xm = (long)a.N >= 2L * a.B * a.Lout;                                       // (hook value 2: only where the weights are twice the rows)
     const int nwa = conv_pw_waves(t.KS);
     if (t.MT == 1 && t.NT == 1 && nwa == 8) return conv_pw_launch_t<1, 1, 8>(a, xm, s);

@@ -686,10 +686,7 @@ hipError_t attn_init_attrs() {
     return hipSuccess;
 }
 
-int g_attn_qb_default = 1;    // QK^T on the bf16 pipe (d = 16 / 32; d = 64 only when asked for) unless MTV_ATT_QB / mtv_debug_attention_qb say otherwise
-int g_attn_qb_force = -1;     // mtv_debug_attention_qb: -1 = environment / default, 0 off, 1 on
-
-hipError_t launch_attention(const AttnArgs& a0, hipStream_t s) {
+hipError_t launch_attention(const AttnArgs& a0, const PlanOptions& o, hipStream_t s) {
     AttnArgs a = a0;
     const int d = a.C / a.H;
     // (round 3's all-bf16 split core k_attention_b3 -- parity-green, 0-40 % slower at every shape -- left the product in round 6:
@@ -710,14 +707,9 @@ hipError_t launch_attention(const AttnArgs& a0, hipStream_t s) {
     // segments differ in length (the plane attention of a [xy | yt | xt] clip: the xy workgroups walk twice the keys):
     // 512 half-size workgroups, two per CU, let the dispatcher even that out (measured 19.2 -> 16.3 us at L = 2048, d = 16;
     // with ONE segment the same change costs 2 us: twice the K/V staging for nothing).  MTV_ATT_QW=2|4 forces either.
-    static int wide_qw = -1;
-    if (wide_qw < 0) {
-        wide_qw = 0;
-        if (const char* e = getenv("MTV_ATT_QW")) wide_qw = atoi(e) == 2 ? 2 : (atoi(e) == 4 ? 4 : 0);
-    }
     bool uneven = false;
     for (int i = 1; i < a.nseg && !a.seg_uniform; ++i) uneven |= a.seg_len[i] != a.seg_len[0];
-    const bool half = wide && (d == 16 || d == 32) && (wide_qw == 2 || (wide_qw == 0 && uneven && blocks64 * a.H * a.B <= 256));
+    const bool half = wide && (d == 16 || d == 32) && (o.att_qw == 2 || (o.att_qw == 0 && uneven && blocks64 * a.H * a.B <= 256));
     const int qw = wide ? (half ? 2 : 4) : 1;
     a.blk_prefix[0] = 0;
     if (a.seg_uniform) {
@@ -740,27 +732,14 @@ hipError_t launch_attention(const AttnArgs& a0, hipStream_t s) {
     // hand-overs, a prefetch distance longer than the load latency, and -- d = 64, short segments -- four key parts
     // (waves) per workgroup instead of two.  With more workgroups than CUs the smaller footprint (3-4 resident
     // workgroups per CU) hides latency better and stays.  MTV_ATT_KBX=1 switches it off.
-    static int kbx_env = -1;
-    if (kbx_env < 0) {
-        kbx_env = 2;
-        if (const char* e = getenv("MTV_ATT_KBX")) kbx_env = atoi(e) == 1 ? 1 : (atoi(e) == 3 ? 3 : 2);      // (3: double blocks at every grid size -- experiment)
-    }
     int maxk = a.kv ? a.Lkv : a.seg_uniform;
     if (!a.kv && !a.seg_uniform)
         for (int i = 0; i < a.nseg; ++i) maxk = a.seg_len[i] > maxk ? a.seg_len[i] : maxk;
     const int base_kb = d >= 64 ? 32 : (d >= 32 ? 64 : 128);
-    const bool big = kbx_env >= 2 && !half && (d == 16 || d == 32 || d == 64) && ((long)nblk * a.H * a.B <= 256 || kbx_env == 3) && maxk > base_kb;
-    // QK^T on the bf16 matrix pipe (three-term split of q and k, f32 accuracy; k_attention<..., QB = 1>) for the 8-wave shapes of
-    // d = 16 / 32 / 64: MTV_ATT_QB=0 switches it off, =1 on everywhere.
-    // Default: on for d = 16 / 32 (level-0 / -1 attentions: -12 ... -17 % per launch at 2048+ keys, profiles/r03_attention_qb.txt),
-    // off for d = 64 (the autoencoder: bound by its V^T staging, no gain) unless asked for explicitly.
-    static int qb_env = -1, qb_explicit = 0;
-    if (qb_env < 0) {
-        qb_env = g_attn_qb_default;
-        if (const char* e = getenv("MTV_ATT_QB")) { qb_env = atoi(e) != 0 ? 1 : 0; qb_explicit = 1; }
-    }
-    const bool qb_asked = g_attn_qb_force == 1 || (g_attn_qb_force < 0 && qb_explicit && qb_env == 1);
-    const bool qb = d == 64 ? qb_asked : (g_attn_qb_force >= 0 ? g_attn_qb_force : qb_env) != 0;
+    const bool big = o.att_kbx >= 2 && !half && (d == 16 || d == 32 || d == 64) && (long)nblk * a.H * a.B <= 256 && maxk > base_kb;
+    // QK^T on the bf16 matrix pipe (three-term split of q and k, f32 accuracy; QB = 1) for the 8-wave shapes.  Default: on for d = 16 / 32 (-12 ... -17 % per
+    // launch at 2048+ keys, profiles/r03_attention_qb.txt), off for d = 64 (the autoencoder: bound by its V^T staging, no gain) unless asked for.
+    const bool qb = o.att_qb < 0 ? d != 64 : o.att_qb != 0;
 #define MTV_ATT_GO(D, QW, KSP, KBX) return att_launch<D, QW, KSP, KBX>(a, grid, s)
 #define MTV_ATT_GOQ(D, QW, KSP, KBX) do { if (qb) return att_launch<D, QW, KSP, KBX, 1>(a, grid, s); return att_launch<D, QW, KSP, KBX>(a, grid, s); } while (0)
     switch (d) {

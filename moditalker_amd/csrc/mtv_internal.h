@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "options.h"
+
 namespace mtv {
 
 // Plane boundaries inside one batch element's token axis: [0,b1) xy (r x r), [b1,b2) yt (t x r),
@@ -121,7 +123,6 @@ struct ConvArgs {
     const DdimFuse* ddim;    // sampler-step head only (nullptr otherwise)
     const int* step_counter; // ... the device-side step index (DdimFuse::counter; here too so it is loaded at entry)
     unsigned long long* dbg; // phase timestamps for tools/ubench/conv_bench (nullptr in the product)
-    long long dbg_stat_dup;  // 0 in the product: offset (doubles) of the other step parity's statistics arena (MTV_DEBUG_STATDUP timing experiment)
 };
 static_assert(sizeof(ConvArgs) <= 512, "touch_kernargs takes its eight-line form (profiles/r07_retire_k_lin_step_ab.txt: what a ninth line costs)");
 
@@ -531,7 +532,7 @@ bool conv_win_tile_exists(const ConvTile& t);
 bool conv_win_can_run(const ConvArgs& a, const ConvTile& t, size_t slab_cap);
 int conv_win_selftest(int r, int t, bool up, int Lout, int Lsrc);      // host-only check of the window arithmetic (0 = ok)
 size_t conv_win_smem_bytes(const ConvArgs& a, ConvTile t);
-hipError_t launch_conv_win(const ConvArgs& a, ConvTile t, hipStream_t s);
+hipError_t launch_conv_win(const ConvArgs& a, ConvTile t, const PlanOptions& o, hipStream_t s);
 bool win_pack_valid(const WinPack& p);
 int win_pack_selftest(const WinPack& p);                               // host-only check of win_pack_source against the kernel's load arithmetic (0 = ok)
 hipError_t launch_win_repack(const float* W, int ldw, float* dst, const WinPack& p, hipStream_t s);   // legacy [krow][ldw] -> ConvArgs::Wwin
@@ -539,19 +540,18 @@ bool conv_pw_eligible(const ConvArgs& a, int MT, int NTW, int wcode = 1);     //
 bool conv_pw_tile_exists(const ConvTile& t);
 bool conv_pw_can_run(const ConvArgs& a, const ConvTile& t, size_t slab_cap);
 size_t conv_pw_smem_bytes(const ConvArgs& a, ConvTile t);
-hipError_t launch_conv_pw(const ConvArgs& a, ConvTile t, hipStream_t s);
+hipError_t launch_conv_pw(const ConvArgs& a, ConvTile t, const PlanOptions& o, hipStream_t s);
 bool conv_lds_eligible(const ConvArgs& a);
 bool conv_tile_exists(const ConvTile& t);
 bool conv_tile_runs(const ConvArgs& a, const ConvTile& t, size_t slab_cap);
-ConvTile conv_pick_tile(int B, int Lout, int N, int nchunks, int Cmain, bool has_gn);
+ConvTile conv_pick_tile(const PlanOptions& o, int B, int Lout, int N, int nchunks, int Cmain, bool has_gn);
 size_t conv_smem_bytes(const ConvArgs& a, ConvTile t);
-hipError_t launch_conv(const ConvArgs& a, ConvTile t, hipStream_t s);
+hipError_t launch_conv(const ConvArgs& a, ConvTile t, const PlanOptions& o, hipStream_t s);
 hipError_t conv_init_attrs();
 hipError_t attn_init_attrs();
 hipError_t launch_gn_stats(const StatsArgs& a, hipStream_t s);
 hipError_t launch_pool_down(const PoolArgs& a, hipStream_t s);
-hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
-extern int g_attn_qb_default, g_attn_qb_force;   // k_attention<..., QB>: QK^T on the bf16 matrix pipe (kernels.hip)
+hipError_t launch_attention(const AttnArgs& a, const PlanOptions& o, hipStream_t s);
 // deep levels (deep.hip)
 struct DeepTile { int RT, NT; };                 // k_deep_conv<RT, NT>: 16 RT rows x 16 NT columns per workgroup
 size_t deep_weight_floats(const DeepArgs& a, int NT);
@@ -562,10 +562,10 @@ namespace mtv {
 std::vector<int> deep_rowtab(const DeepArgs& a, DeepTile t);   // host: the row table of a configured conv (upload it, pass it as DeepArgs::rowtab)
 bool deep_configure(DeepArgs& a, DeepTile* t);   // picks row groups / K slices (<= 8) / tile; false: this conv stays on k_conv
 size_t deep_smem_bytes(const DeepArgs& a, DeepTile t);
-hipError_t launch_deep_conv(const DeepArgs& a, DeepTile t, hipStream_t s);
+hipError_t launch_deep_conv(const DeepArgs& a, DeepTile t, const PlanOptions& o, hipStream_t s);
 hipError_t launch_deep_repack(const float* W, int ldw, float* dst, const DeepArgs& a, int NT, hipStream_t s);   // legacy [krow][ldw] -> deep layout
 hipError_t launch_deep_finalize(const DeepFinArgs& a, hipStream_t s);
-bool deep_attn_configure(DeepAttnArgs& a);                // fills HPW / NC / group counts; false: this block keeps k_attention + a proj conv
+bool deep_attn_configure(DeepAttnArgs& a, const PlanOptions& o);              // fills HPW / NC / group counts; false: this block keeps k_attention + a proj conv
 hipError_t launch_deep_attn(const DeepAttnArgs& a, hipStream_t s);
 hipError_t deep_init_attrs();
 // whole attention block of a deep level in one launch (block.hip)

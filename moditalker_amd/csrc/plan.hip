@@ -198,16 +198,8 @@ static bool table_matches_formula(const std::vector<int>& h, int ntaps, bool upm
 // =====================================================================================
 // plan builder
 // =====================================================================================
-static int g_deep_mode = -1;       // mtv_debug_deep: -1 = MTV_DEEP / default (on), 0 = every conv on k_conv, 1 = on
-static int g_resident_override = 0; // mtv_debug_resident_cus: > 0 = contexts created afterwards plan for that many co-resident CUs
-static int g_deep_attn_form = -1;  // mtv_debug_deep_attn_form: -1 / 0 = deep_attn_configure's rule (MTV_DEEP_ATTN_HPW), 1 / 2 = DeepAttnArgs::form
-static int g_deep_opts = -1;       // mtv_debug_deep_options: -1 = the MTV_DEEP_* environment / defaults, else a bit mask (MTV_DEEP_OPT_*)
-static bool deep_opt(int bit, const char* env, bool dflt) {
-    if (g_deep_opts >= 0) return (g_deep_opts & bit) != 0;
-    const char* e = getenv(env);
-    return e ? atoi(e) != 0 : dflt;
-}
-static bool deep_forced_off();     // (a forced legacy tile -- testing aids below -- keeps every conv on the kernel under test)
+// (a forced legacy tile keeps every conv on the kernel under test; not force_win / force_pw: those kernels serve the large levels)
+static bool deep_forced_off(const PlanOptions& o) { return o.force_tile[0] > 0 || o.force_lds[0] > 0 || o.force_b3[0] > 0; }
 
 namespace {
 
@@ -217,6 +209,7 @@ struct Builder {
     int B;
     int mode;
     const mtv_config& f;
+    const PlanOptions& opt;   // the context's settings: the op closures below hold a pointer to them (they live as long as the context)
     int emb;
     float* film_out;     // FORWARD: [maxB][film_total]; sampler step: [film_total] shared by every clip of the call
     int film_stride;     // floats between batch elements of film_out (0 in a sampler step)
@@ -228,7 +221,7 @@ struct Builder {
     std::map<const float*, Tens> fin_cache;                        // deep tensor (slab 0) -> its plain copy, made once
 
     Builder(mtv_ctx* ctx, Plan* p, int batch, int md)
-        : c(ctx), plan(p), B(batch), mode(md), f(ctx->cfg), emb(ctx->emb_dim), film_out(nullptr), film_stride(0) {}
+        : c(ctx), plan(p), B(batch), mode(md), f(ctx->cfg), opt(ctx->opt), emb(ctx->emb_dim), film_out(nullptr), film_stride(0) {}
 
     void push(const std::string& name, std::function<hipError_t(hipStream_t)> fn, double flops = 0.0, double bytes = 0.0) {
         Op op;
@@ -275,10 +268,7 @@ struct Builder {
         a0.B = B;
         a0.seg_out = c->lv[lvl_out].seg();
         a0.stat_cstride = (unsigned)c->stats_copy_doubles;
-        if (mode == MODE_STEP0 || mode == MODE_STEP1)      // (timing experiment MTV_DEBUG_STATDUP, launch_conv: where the other parity's arena lies)
-            a0.dbg_stat_dup = (mode == MODE_STEP0 ? 1 : -1) * (long long)(c->stats_bytes / sizeof(double));
-        static const bool geo_env = []() { const char* e = getenv("MTV_GEO"); return !e || atoi(e) != 0; }();
-        if (c->geo_ok && geo_env) {                 // gather tables -> arithmetic (checked equal in mtv_create)
+        if (c->geo_ok && opt.geo) {                 // gather tables -> arithmetic (checked equal in mtv_create)
             const int lo = lvl_out;
             a0.geo_r = c->lv[lo].r;
             a0.geo_t = c->lv[lo].t;
@@ -295,15 +285,14 @@ struct Builder {
             a0.gn.inv_n[2] = 1.0 / ((double)(sg.L - sg.b2) * gs);
             a0.gn.inv_n[3] = 1.0 / ((double)sg.L * gs);
         }
-        if (x3_wanted((long)B * a0.Lout))          // split-bf16 copy of the weights for the large-token-count kernel k_conv_x3
+        if (x3_wanted(opt, (long)B * a0.Lout))          // split-bf16 copy of the weights for the large-token-count kernel k_conv_x3
             a0.W3 = c->w3_for(a0.W, a0.ntaps * a0.Cmain + a0.Cskip, a0.ldw, &a0.w3_plane);
         account_conv(a0);
-        static const bool stamps_env = getenv("MTV_STAMPS") != nullptr;      // diagnostic build only (mtv_debug_stamps)
-        if (stamps_env) a0.dbg = reinterpret_cast<unsigned long long*>(c->buf("dbg." + name + "." + std::to_string(mode) + "." + std::to_string(B), 128));
+        if (opt.stamps) a0.dbg = reinterpret_cast<unsigned long long*>(c->buf("dbg." + name + "." + std::to_string(mode) + "." + std::to_string(B), 128));
         auto op = std::make_shared<ConvOp>();
         op->a = a0;
-        op->t = conv_pick_tile(B, a0.Lout, a0.N, nchunks, a0.Cmain, a0.gn.sums != nullptr);
-        force_family_tile(a0, &op->t);
+        op->t = conv_pick_tile(opt, B, a0.Lout, a0.N, nchunks, a0.Cmain, a0.gn.sums != nullptr);
+        force_family_tile(opt, a0, &op->t);
         if (attach_win_pack(c, op.get()) != MTV_OK) err = "packed 3x3 weight copy failed at " + name;
         op->base_name = std::string(a0.ntaps == 9 ? "conv3:" : "conv1:") + name;
         op->op_index = (int)plan->ops.size();
@@ -313,15 +302,13 @@ struct Builder {
         const double flops = 2.0 * B * a0.Lout * a0.N * K;
         const double bytes = 4.0 * (K * a0.N + a0.N) +
                              4.0 * B * ((double)a0.Lsrc * a0.Cmain + (double)a0.Lskip * a0.Cskip + (double)a0.Lout * a0.N + (a0.res ? (double)a0.Lout * a0.N : 0.0));
-        push(op->base_name + conv_tag(op->a, op->t), [op](hipStream_t s) { return launch_conv(op->a, op->t, s); }, flops, bytes);
+        push(op->base_name + conv_tag(op->a, op->t), [op, o = &opt](hipStream_t s) { return launch_conv(op->a, op->t, *o, s); }, flops, bytes);
     }
 
 
     // ---- deep levels (deep.hip): K-sliced convs whose consumers add the partial slabs and compute the GroupNorm statistics ----
     bool deep_on(int lvl) const {
-        static const bool env = []() { const char* e = getenv("MTV_DEEP"); return !e || atoi(e) != 0; }();
-        const bool on = g_deep_mode < 0 ? env : g_deep_mode != 0;
-        return on && !deep_forced_off() && B <= 2 && c->lv[lvl].L <= 128;
+        return opt.deep && !deep_forced_off(opt) && B <= 2 && c->lv[lvl].L <= 128;
     }
     int deep_clips() const { return c->cfg.max_batch < 2 ? c->cfg.max_batch : 2; }     // clips per slab: the deep path only runs with B <= 2
     static DeepSrc dsrc(const Tens& t) { return DeepSrc{t.p, t.slab, t.ks, t.C}; }
@@ -398,7 +385,7 @@ struct Builder {
         const double K = (double)a.ntaps * a.Cmain + a.Cskip;
         const double flops = 2.0 * B * a.Lout * a.N * K;
         const double bytes = 4.0 * (K * a.N + a.N) + 4.0 * B * ((double)a.Lsrc * a.Cmain + (double)a.Lout * a.Cskip + (double)a.Lout * a.N + (a.res.p ? (double)a.Lout * a.N : 0.0));
-        push(std::string(a.ntaps == 9 ? "conv3:" : "conv1:") + name + deep_tag(a, t), [op](hipStream_t s) { return launch_deep_conv(op->a, op->t, s); }, flops, bytes);
+        push(std::string(a.ntaps == 9 ? "conv3:" : "conv1:") + name + deep_tag(a, t), [op, o = &opt](hipStream_t s) { return launch_deep_conv(op->a, op->t, *o, s); }, flops, bytes);
         if (out.ks > 1) deep_producer[out.p] = op;
         return out;
     }
@@ -419,7 +406,7 @@ struct Builder {
         long ntile = 0, nwg = 0;
         int nslices = 0, lastN = 0;
         bool tile_ok = true;
-        if (!deep_opt(MTV_DEEP_OPT_FIN_PASS, "MTV_DEEP_FIN_PASS", false)) {
+        if (!opt.deep_fin_pass) {
             auto dp = deep_producer.find(x.p);
             auto ap = attn_producer.find(x.p);
             if (dp != deep_producer.end()) {
@@ -554,7 +541,7 @@ struct Builder {
             // ResBlock(down=True) (unet.py:179-184, Downsample = AvgPool2d :594): round 5 folds both 2x2 means into the two convs -- conv1
             // stages the finer level's rows, applies GroupNorm / SiLU there and pools in LDS; conv2's residual is the pooled raw input, shared
             // out over its K slices.  No k_pool_down launch, no plain copy of the input, no statistics site.  MTV_DEEP_POOL_FOLD=0: round 4's form.
-            static const bool fold_env = []() { const char* e = getenv("MTV_DEEP_POOL_FOLD"); return !e || atoi(e) != 0; }();
+            const bool fold_env = opt.deep_pool_fold != 0;
             const bool fold = down && fold_env && x.size() == 1 && !has_skip_conv && Li.r == 2 * Lo.r && Li.t == 2 * Lo.t;     // (even planes only)
             DeepArgs a1 = deep_args(lvl_out, 9, r.cout, cb1);
             a1.Cmain = cin;
@@ -747,12 +734,11 @@ struct Builder {
         if (c->accounting) c->work.flops_attn_core += aflops1;
         char tag[64];
         snprintf(tag, sizeof tag, "[L%d d%d %s]", L.L, d, whole ? "1d" : "2d");      // (which core runs is decided at launch: launch_attention)
-        static const bool att_stamps = getenv("MTV_STAMPS") != nullptr;       // diagnostic build only (mtv_debug_stamps)
-        if (att_stamps) {
+        if (opt.stamps) {                          // diagnostic build only (mtv_debug_stamps)
             t.dbg = reinterpret_cast<unsigned long long*>(c->buf("dbg.attn." + nm + "." + std::to_string(mode) + "." + std::to_string(B), 128));
             plan->attn_dbg.emplace_back("attn:" + nm + tag, t.dbg);
         }
-        push("attn:" + nm + tag, [t](hipStream_t s) { return launch_attention(t, s); }, B * aflops1, 4.0 * B * L.L * 4.0 * C);
+        push("attn:" + nm + tag, [t, o = &opt](hipStream_t s) { return launch_attention(t, *o, s); }, B * aflops1, 4.0 * B * L.L * 4.0 * C);
     }
 
     Tens attention(const Tens& x0, const std::string& P, bool whole, const std::string& nm) {
@@ -784,11 +770,11 @@ struct Builder {
         const float scale = 1.0f / std::sqrt(std::sqrt((float)d));
         const double aflops1 = attn_flops(L, whole, H, d), aflops = B * aflops1;      // per clip | per launch
 
-        const bool fuse_env = !deep_opt(MTV_DEEP_OPT_NO_FUSED_ATTN, "MTV_DEEP_NO_ATTN", false);
+        const bool fuse_env = !opt.deep_no_attn;
         // ---- the whole block in ONE launch (block.hip, k_deep_block): a cluster of workgroups per (clip, head) reads the input's slabs,
         // computes its GroupNorm statistics, the head's q | k | v (K-sliced inside the cluster, two in-launch hand-offs), the attention and
         // the head's share of proj_out -> output slab `head`.  No finalize pass, no statistics site, no plain qkv tensor.
-        const bool block_env = !deep_opt(MTV_DEEP_OPT_NO_BLOCK, "MTV_DEEP_NO_BLOCK", false) && fuse_env;
+        const bool block_env = !opt.deep_no_block && fuse_env;
         if (deep_on(lvl) && block_env) {
             DeepBlockArgs ba{};
             ba.x = dsrc(x0);
@@ -796,14 +782,11 @@ struct Builder {
             ba.scale = scale;
             ba.gamma = gw; ba.beta = gb; ba.gs = C / 32;
             ba.Wq = wq.nk; ba.bq = bq; ba.Wp = wp.nk; ba.bp = bp;
-            static const int force_cl = []() { const char* e = getenv("MTV_BLOCK_CL"); return e ? atoi(e) : 0; }();
+            const int force_cl = opt.block_cl, force_rq = opt.block_rq;
             // Where it pays (profiles/r05_deep_block.txt: the block in one launch against fin + qkv + k_deep_attn of round 4, same graph
             // chains): 32 tokens 15.7 us against 21.1, [128 x 256] 21.2 against 26.8 -- but [128 x 512] 33 against 27.5: there the K slices'
             // partial q | k | v rows are 12.6 MB of hand-off traffic per block.  MTV_BLOCK_MAX_L / MTV_BLOCK_MAX_LC override the rule.
-            static const int max_l = []() { const char* e = getenv("MTV_BLOCK_MAX_L"); return e ? atoi(e) : 32; }();
-            static const long max_lc = []() { const char* e = getenv("MTV_BLOCK_MAX_LC"); return e ? atol(e) : 128L * 256; }();
-            const bool pays = L.L <= max_l || (long)L.L * C <= max_lc || deep_opt(MTV_DEEP_OPT_BLOCK_ALL, "MTV_DEEP_BLOCK_ALL", false);
-            static const int force_rq = []() { const char* e = getenv("MTV_BLOCK_RQ"); return e ? atoi(e) : 0; }();
+            const bool pays = L.L <= opt.block_max_l || (long)L.L * C <= opt.block_max_lc || opt.deep_block_all;
             const int max_wgs = std::min(128, c->resident_cus / 2);        // all workgroups of the launch resident together, on half of what the launch may use
             if (pays && (deep_block_configure(ba, force_cl, force_rq, max_wgs) || ((force_cl || force_rq) && deep_block_configure(ba, 0, 0, max_wgs)))) {
                 const Tens out = out_slabs(nm + ".out", lvl, C, H);
@@ -842,8 +825,8 @@ struct Builder {
         da.scale = scale;
         da.Wp = wp.w; da.ldw = wp.ld; da.bias = bp;
         da.Wpk = wp.pk;                                         // (the proj B fragments go straight into registers)
-        da.form = g_deep_attn_form > 0 ? g_deep_attn_form : 0;
-        const bool fused = deep_on(lvl) && fuse_env && deep_attn_configure(da);
+        da.form = opt.deep_attn_form;
+        const bool fused = deep_on(lvl) && fuse_env && deep_attn_configure(da, opt);
         const Tens x = materialize(x0, nm + ".in");       // k_conv reads a plain tensor and the statistics its producer left
         double* site = c->new_site();
         add_stats({x}, lvl, site);
@@ -1023,53 +1006,21 @@ struct Builder {
 
 // Empirical tile selection: every distinct conv shape of the plan is timed once over the valid
 // (MT, NT, NW, KS) candidates with its real arguments (MTV_AUTOTUNE=0 keeps the analytic pick).
-// testing aids: a forced tile of one kernel family runs every conv of plans built afterwards that the family can run on that tile; a conv that
-// turns out not to be eligible at launch falls back (launch_conv).  Set from the environment (read once, on first use) or by mtv_debug_force_*:
-// both go through force_set, so a value one accepts the other accepts.
-struct ForcedTile {
-    const char* env;        // "MT,NT[,KS]"
-    ConvFamily fam;
-    int v[3];               // MT (-1: environment not read yet, 0: off), NT, KS
-};
-static ForcedTile g_force_win{"MTV_FORCE_WIN", CONV_WIN, {-1, 0, 1}};     // every eligible 3x3 conv on k_conv_win<MT, NT>, KS K slices where the conv can take them
-static ForcedTile g_force_pw{"MTV_FORCE_PW", CONV_PW, {-1, 0, 1}};        // every eligible 1x1 conv on k_conv_pw<MT, NTW>; third number: multiplying waves (1 or 8 = all)
-static ForcedTile g_force_b3{"MTV_FORCE_B3", CONV_X3, {-1, 0, 1}};        // every eligible conv on the split-bf16 kernel k_conv_x3<MT, NT>
-static ForcedTile g_force_lds{"MTV_FORCE_LDS", CONV_LDS, {-1, 0, 1}};     // every eligible conv on the LDS-tiled kernel k_conv_lds<WM, WN>
-static bool force_set(ForcedTile& f, int mt, int nt, int ks) {
-    if (mt == 0) { f.v[0] = 0; return true; }
-    if (f.fam == CONV_PW && ks == 8) ks = 1;
-    if (!conv_tile_exists(ConvTile{mt, nt, f.fam, ks, 0})) return false;
-    f.v[0] = mt; f.v[1] = nt; f.v[2] = ks;
-    return true;
-}
-static const ForcedTile& force_env(ForcedTile& f) {
-    if (f.v[0] == -1) {
-        f.v[0] = 0;
-        int x = 0, y = 0, z = 1;
-        const char* e = getenv(f.env);
-        if (e && sscanf(e, "%d,%d,%d", &x, &y, &z) >= 2) force_set(f, x, y, z);
-    }
-    return f;
-}
+// (a forced tile, opt.force_*: a conv that turns out not to be eligible at launch falls back, launch_conv; tuner and tile table are off for the context)
 // Convs of at least X3_MIN_ROWS tokens (all clips together) get a split-bf16 weight copy + activation scratch and are offered to
 // the tuner on k_conv_x3; below that the elementwise pass and the few 128-row tiles cannot pay (profiles/r03_conv_x3_bench.txt).
 // A forced tile (tests) lifts the bound.
-bool x3_wanted(long rows) { return rows >= X3_MIN_ROWS || force_env(g_force_b3).v[0] > 0; }
+bool x3_wanted(const PlanOptions& o, long rows) { return rows >= X3_MIN_ROWS || o.force_b3[0] > 0; }
 // (... but never the one-clip step at R = 32, the metric's workload: it stays on the exact-f32 instruction throughout)
 static bool x3_tuner_offers(const ConvArgs& a) { return !(a.B == 1 && a.Lout <= 2048); }
-static bool deep_forced_off() {
-    return g_force_lds.v[0] > 0 || force_env(g_force_b3).v[0] > 0 || getenv("MTV_FORCE_TILE") || getenv("MTV_FORCE_LDS");     // (not MTV_FORCE_WIN: k_conv_win serves
-                                                                                                                             //  the large levels)
-}
 // k_conv_win's packed weight copy for the tile an op runs on (ConvArgs::Wwin; round 9): attached when the tile is final -- the builder's (a forced tile included)
-// or the table's / the tuner's --, dropped when the op moves to another family.  MTV_WIN_PACKED=0, read here at every plan build (an A/B hook: one process can
-// hold a plan of each form), leaves the plan on the reads from ConvArgs::W.
+// or the table's / the tuner's --, dropped when the op moves to another family.  opt.win_packed = 0 (an A/B hook: one process can hold a context of
+// each form) leaves the plans on the reads from ConvArgs::W.
 int attach_win_pack(mtv_ctx* c, ConvOp* op) {
     ConvArgs& a = op->a;
     a.Wwin = nullptr;
     a.wwin_shape = 0;
-    const char* env = getenv("MTV_WIN_PACKED");
-    if ((env && atoi(env) == 0) || conv_family(op->t) != CONV_WIN || !conv_win_can_run(a, op->t, CONV_SLAB_ANY)) return MTV_OK;
+    if (!c->opt.win_packed || conv_family(op->t) != CONV_WIN || !conv_win_can_run(a, op->t, CONV_SLAB_ANY)) return MTV_OK;
     const WinPack lay{op->t.NT, op->t.KS < 1 ? 1 : op->t.KS, a.Cmain, a.Cskip, a.N};
     const float* p = c->wwin_for(a.W, a.ldw, lay);
     if (!p) return fail(MTV_ERR_HIP, "packed 3x3 weight copy (k_conv_win): " + std::string(mtv_last_error()));
@@ -1078,14 +1029,14 @@ int attach_win_pack(mtv_ctx* c, ConvOp* op) {
     return MTV_OK;
 }
 
-void force_family_tile(const ConvArgs& a, ConvTile* t) {
-    static const int win_xm = getenv("MTV_FORCE_WIN_XM") ? atoi(getenv("MTV_FORCE_WIN_XM")) != 0 : 0;      // (k_conv_win with the XCD-aware block order)
-    for (ForcedTile* f : {&g_force_win, &g_force_pw, &g_force_b3, &g_force_lds}) {      // (in this order: the first family that can run the conv takes it)
-        if (force_env(*f).v[0] <= 0) continue;
-        ConvTile ft{f->v[0], f->v[1], f->fam, f->v[2], f->fam == CONV_WIN ? win_xm : 0};
+void force_family_tile(const PlanOptions& o, const ConvArgs& a, ConvTile* t) {
+    const struct { const int* v; ConvFamily fam; } forced[] = {{o.force_win, CONV_WIN}, {o.force_pw, CONV_PW}, {o.force_b3, CONV_X3}, {o.force_lds, CONV_LDS}};
+    for (const auto& f : forced) {             // (in this order: the first family that can run the conv takes it)
+        if (f.v[0] <= 0) continue;
+        ConvTile ft{f.v[0], f.v[1], f.fam, f.v[2], f.fam == CONV_WIN ? o.force_win_xm : 0};
         // (K slices where the conv can take them -- k_conv_win: no fused skip conv, whole chunks per slice; k_conv_x3: at least 6 chunks each --
         // else the unsliced tile; the slab is sized after the tiles are chosen, finish_split_k)
-        if (conv_ks_is_slices(f->fam) && !conv_tile_runs(a, ft, CONV_SLAB_ANY)) ft.KS = 1;
+        if (conv_ks_is_slices(f.fam) && !conv_tile_runs(a, ft, CONV_SLAB_ANY)) ft.KS = 1;
         if (conv_tile_runs(a, ft, CONV_SLAB_ANY)) { *t = ft; return; }
     }
 }
@@ -1135,7 +1086,7 @@ int finish_split_k(mtv_ctx* c, Plan* plan) {
 
 // Tile table.  moditalker_amd/csrc/tune_gfx950.txt (committed, next to the library) holds the measured best tile
 // of every conv shape of the BASELINE configurations, so a fresh process reproduces the same launch plan without
-// timing anything; shapes it does not list are tuned on first use.  MTV_TUNE_CACHE=<file> replaces it (and is
+// timing anything; shapes it does not list are tuned on first use.  MTV_TUNE_CACHE=<file> (opt.tune_cache) replaces it (and is
 // appended to: that is how the committed table is regenerated, tools/make_tune_table.sh).
 static std::string default_tune_path() {
     Dl_info di;
@@ -1150,8 +1101,7 @@ static std::string default_tune_path() {
 static void tune_cache_load(mtv_ctx* c) {
     if (c->tune_cache_loaded) return;
     c->tune_cache_loaded = true;
-    const char* env = getenv("MTV_TUNE_CACHE");
-    const std::string path = env ? std::string(env) : default_tune_path();
+    const std::string path = c->opt.tune_cache.empty() ? default_tune_path() : c->opt.tune_cache;
     if (FILE* f = fopen(path.c_str(), "r")) {
         char line[256];
         while (fgets(line, sizeof line, f)) {
@@ -1166,10 +1116,9 @@ static void tune_cache_load(mtv_ctx* c) {
     }
 }
 
-static void tune_cache_append(const char* key, const ConvTile& t) {
-    const char* path = getenv("MTV_TUNE_CACHE");
-    if (!path) return;
-    if (FILE* f = fopen(path, "a")) {
+static void tune_cache_append(const std::string& path, const char* key, const ConvTile& t) {
+    if (path.empty()) return;
+    if (FILE* f = fopen(path.c_str(), "a")) {
         fprintf(f, "%s|%d %d %d %d %d\n", key, t.MT, t.NT, t.NW, t.KS, t.XM);
         fclose(f);
     }
@@ -1193,8 +1142,8 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
     if (p->tuned) return MTV_OK;
     p->tuned = true;
     tune_cache_load(c);
-    const char* env = getenv("MTV_AUTOTUNE");
-    if ((env && atoi(env) == 0) || getenv("MTV_FORCE_TILE") || g_force_lds.v[0] > 0 || g_force_b3.v[0] > 0 || g_force_win.v[0] > 0 || g_force_pw.v[0] > 0) return MTV_OK;
+    const PlanOptions& opt = c->opt;
+    if (!opt.autotune || opt.any_forced_tile()) return MTV_OK;
     static const int cand[][2] = {{4, 4}, {2, 4}, {1, 4}, {2, 2}, {1, 2}, {1, 1}};
     struct Events {             // destroyed on every exit path (HIPCHK returns early)
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1206,7 +1155,7 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
     HIPCHK(hipEventCreate(&ev.e0));
     HIPCHK(hipEventCreate(&ev.e1));
     hipEvent_t e0 = ev.e0, e1 = ev.e1;
-    static const int nsamp = []() { const char* e = getenv("MTV_TUNE_SAMPLES"); const int v = e ? atoi(e) : 5; return v < 1 ? 1 : (v > 15 ? 15 : v); }();
+    const int nsamp = opt.tune_samples;
     const size_t slab_cap = p->slab_floats;
     if (!c->flush) {
         c->flush_bytes = (size_t)320 << 20;
@@ -1217,7 +1166,7 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
         ConvArgs a = op->a;
         a.ddim = nullptr;       // the tuner times the conv itself, not the step hand-over
         a.Wwin = nullptr;       // ... and its k_conv_win candidates on the legacy reads: the packed copy is made for the ONE tile that wins (below)
-        auto run = [&](const ConvTile& tt) -> hipError_t { return op->tune_launch ? op->tune_launch(a, tt, s) : launch_conv(a, tt, s); };
+        auto run = [&](const ConvTile& tt) -> hipError_t { return op->tune_launch ? op->tune_launch(a, tt, s) : launch_conv(a, tt, opt, s); };
         char key[176];
         snprintf(key, sizeof key, "B%d L%d/%d/%d N%d t%d C%d+%d gn%d f%d r%d s%d cm%d", a.B, a.Lout, a.Lsrc, a.Lskip, a.N, a.ntaps, a.Cmain, a.Cskip,
                  a.gn.sums ? 1 : 0, a.gn.film ? 1 : 0, a.res ? 1 : 0, a.nstat, a.out_cm);
@@ -1350,7 +1299,7 @@ int autotune(mtv_ctx* c, Plan* p, hipStream_t s) {
                     }
             }
             it = c->tune_cache.emplace(key, best).first;
-            tune_cache_append(key, best);
+            tune_cache_append(c->opt.tune_cache, key, best);
         }
         op->t = it->second;
         p->ops[op->op_index].name = op->base_name + Builder::conv_tag(op->a, op->t);
@@ -1395,6 +1344,7 @@ int mtv_version(void) { return 1; }
 }  // extern "C"
 
 int ctx_init_common(mtv_ctx* c) {
+    c->opt = options_snapshot();     // environment and mtv_debug_* overrides as they are NOW: this context keeps them for life
     HIPCHK(hipGetDevice(&c->device));
     if (!c->cap_stream) HIPCHK(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
     HIPCHK(conv_init_attrs());     // dynamic LDS above 64 KB must be opted into once per kernel (never under capture)
@@ -1406,8 +1356,7 @@ int ctx_init_common(mtv_ctx* c) {
         // launch can use: a CPX / DPX partition reports fewer CUs here; a CU-masked stream is checked per call (check_stream_residency).
         int ncu = 0;
         HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-        static const int env_cus = []() { const char* e = getenv("MTV_RESIDENT_CUS"); return e ? atoi(e) : 0; }();
-        const int want = g_resident_override > 0 ? g_resident_override : env_cus;
+        const int want = c->opt.resident_cus;
         c->resident_cus = want > 0 ? std::min(want, ncu > 0 ? ncu : want) : (ncu > 0 ? ncu : 256);
     }
     if (!c->fault_h) {     // device-side fault word (k_deep_block: a hand-off wait that timed out), host-mapped: checked without a copy
@@ -1811,7 +1760,7 @@ int mtv_ddim_sample(mtv_ctx* c, float* x_io, const float* cond, const float* ima
     // step index, its coefficients, its FiLM row and its noise slab are all resolved on the device -- so M consecutive steps can just as
     // well be ONE graph (round 5: M = 8 by default, MTV_STEPS_PER_GRAPH; the hand-over between two graph launches is a few microseconds of
     // idle GPU per launch: profiles/r05_steps_per_graph_ab.txt)
-    static const int M = []() { const char* e = getenv("MTV_STEPS_PER_GRAPH"); const int v = e ? atoi(e) : 8; return v < 1 ? 1 : (v > 32 ? 32 : v & ~1 ? v & ~1 : 1); }();
+    const int M = c->opt.steps_per_graph;
     int i0 = 0;
     if (!c->eager) {
         // every graph this context can need is captured by its FIRST call (the tail of a later call must never pay a capture)
@@ -1860,12 +1809,6 @@ int mtv_check_fault(mtv_ctx* c) {
 int mtv_debug_arm_fault(mtv_ctx* c) {
     if (!c || !c->fault_d) return fail(MTV_ERR_INVALID, "null context");
     c->debug_fault_armed = true;
-    return MTV_OK;
-}
-
-int mtv_debug_resident_cus(int n) {
-    if (n < 0 || n > 4096) return fail(MTV_ERR_INVALID, "resident CUs must be 0 (the device's count / MTV_RESIDENT_CUS) or a positive count");
-    g_resident_override = n;
     return MTV_OK;
 }
 
@@ -2165,50 +2108,6 @@ int mtv_debug_gather_index(int res, int frames, int tok, int ky, int kx, int up)
     if (res <= 0 || frames <= 0 || tok < 0 || tok >= res * res + 2 * frames * res || ky < 0 || ky > 2 || kx < 0 || kx > 2)
         return fail(MTV_ERR_INVALID, "debug_gather_index: bad arguments") - 1;   // (-2: distinct from "padding")
     return geo_source(res, frames, tok, ky, kx, up != 0);
-}
-
-int mtv_debug_deep(int mode) {
-    if (mode < -1 || mode > 1) return fail(MTV_ERR_INVALID, "mode must be -1 (default), 0 (off) or 1 (on)");
-    g_deep_mode = mode;
-    return MTV_OK;
-}
-
-int mtv_debug_deep_options(int mask) {
-    if (mask < -1 || mask > 127 || (mask >= 0 && (mask & 7)))      // (bits 1, 2, 4: retired variants)
-        return fail(MTV_ERR_INVALID, "mask must be -1 (environment / defaults) or a combination of MTV_DEEP_OPT_*");
-    g_deep_opts = mask;
-    return MTV_OK;
-}
-
-int mtv_debug_deep_attn_form(int form) {
-    if (form < -1 || form > 2) return fail(MTV_ERR_INVALID, "form must be -1 (the rule / MTV_DEEP_ATTN_HPW), 1 (one head per workgroup) or 2 (head groups)");
-    g_deep_attn_form = form;
-    return MTV_OK;
-}
-
-int mtv_debug_attention_qb(int mode) {
-    if (mode < -1 || mode > 1) return fail(MTV_ERR_INVALID, "mode must be -1 (default), 0 (off) or 1 (on)");
-    g_attn_qb_force = mode;
-    return MTV_OK;
-}
-
-int mtv_debug_force_b3(int mt, int nt, int ks) {
-    return force_set(g_force_b3, mt, nt, ks) ? MTV_OK : fail(MTV_ERR_INVALID, "no k_conv_x3<MT, NT> of that shape (4,2 8,2 4,4 2,2 4,1 2,1 8,1), or K slices not 1, 2, 4 or 8");
-}
-
-int mtv_debug_force_pw(int mt, int ntw) { return mtv_debug_force_pw_waves(mt, ntw, 1); }
-
-int mtv_debug_force_pw_waves(int mt, int ntw, int waves) {
-    return force_set(g_force_pw, mt, ntw, waves) ? MTV_OK : fail(MTV_ERR_INVALID, "k_conv_pw tile must be {1, 2} x {1, 2} with 8 multiplying waves, or {1, 2} x 1 with 6 / 4 / 2");
-}
-
-int mtv_debug_force_win_ks(int mt, int nt, int ks) {
-    return force_set(g_force_win, mt, nt, ks) ? MTV_OK : fail(MTV_ERR_INVALID, "k_conv_win tile must be 1x2, 1x4, 2x2 or 2x4, with 1, 2 or 4 K slices");
-}
-int mtv_debug_force_win(int mt, int nt) { return mtv_debug_force_win_ks(mt, nt, 1); }
-
-int mtv_debug_force_lds(int wm, int wn) {
-    return force_set(g_force_lds, wm, wn, 1) ? MTV_OK : fail(MTV_ERR_INVALID, "wave tile must be 2 or 4 by 2, 4 or 8");
 }
 
 int mtv_set_eager(mtv_ctx* c, int eager) {

@@ -14,7 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/mtv_hip.h"
+#include "../../include/mtv_hip_debug.h"
 #include "mtv_internal.h"
 
 using namespace mtv;
@@ -136,6 +136,7 @@ struct mtv_ctx {
     mtv_config cfg{};
     int device = 0;
     int kind = CTX_UNET;                        // which C-ABI family owns this context
+    PlanOptions opt;                            // this context's settings, taken once at creation (ctx_init_common; options.h)
     std::shared_ptr<void> ext;                  // CTX_AE: mtv_ae_config; CTX_XATTN / CTX_ATOM: its weight / workspace record -- lives and dies
                                                 // with the context (no process-global side tables, nothing to lock)
     std::vector<Level> lv;
@@ -183,7 +184,7 @@ struct mtv_ctx {
     int* fault_d = nullptr;
     bool debug_fault_armed = false;              // mtv_debug_arm_fault: the next forward / sampler call ends with a launch that raises the fault word
     int resident_cus = 256;                      // CUs a launch of this context may count on being resident TOGETHER (ctx_init_common: the device's
-                                                 // multiProcessorCount, or mtv_debug_resident_cus / MTV_RESIDENT_CUS): bounds every grid whose workgroups
+                                                 // multiProcessorCount, or opt.resident_cus): bounds every grid whose workgroups
                                                  // wait for each other inside the launch (k_deep_block clusters, tagged completion of deep tensors)
     float* staging = nullptr;
     size_t staging_floats = 0;
@@ -244,7 +245,7 @@ struct mtv_ctx {
     std::map<std::string, ConvTile> tune_cache;           // conv shape -> measured best tile
     void* flush = nullptr;                                // cache-flush scratch for cold auto-tune timing
     size_t flush_bytes = 0;
-    bool tune_cache_loaded = false;                       // MTV_TUNE_CACHE=<file>: persisted across processes
+    bool tune_cache_loaded = false;                       // (opt.tune_cache = <file>: persisted across processes)
 
     // ---------------------------------------------------------------- memory helpers
     int dmalloc(void** p, size_t bytes) {
@@ -336,8 +337,8 @@ int finish_split_k(mtv_ctx* c, Plan* p);                   // slab + arrival cou
 int run_ops(mtv_ctx* c, Plan* p, hipStream_t s);
 int capture(mtv_ctx* c, Plan* p, hipGraphExec_t* out);
 constexpr long X3_MIN_ROWS = 1024;
-bool x3_wanted(long rows);                                  // plan.hip: offer this conv to the split-bf16 kernels?
+bool x3_wanted(const PlanOptions& o, long rows);            // plan.hip: offer this conv to the split-bf16 kernels?
 int check_ready(mtv_ctx* c, int batch);                     // (also refreshes the split-bf16 weight copies after a weight load)
 int ctx_init_common(mtv_ctx* c);
-int attach_win_pack(mtv_ctx* c, ConvOp* op);               // ConvArgs::Wwin for the k_conv_win tile an op runs on (MTV_WIN_PACKED=0: none)
-void force_family_tile(const ConvArgs& a, ConvTile* t);   // MTV_FORCE_WIN / _PW / _B3 / _LDS and the mtv_debug_force_* testing aids
+int attach_win_pack(mtv_ctx* c, ConvOp* op);               // ConvArgs::Wwin for the k_conv_win tile an op runs on (opt.win_packed = 0: none)
+void force_family_tile(const PlanOptions& o, const ConvArgs& a, ConvTile* t);   // opt.force_win / _pw / _b3 / _lds

@@ -36,7 +36,7 @@ const XCfg* xcfg_of(const mtv_ctx* c) {      // owned by the context (mtv_ctx::e
 }
 int pad64(int n) { return (n + 63) / 64 * 64; }
 
-hipError_t gemm(const float* in, int K, const float* W, int ld, const float* bias, int N, float* out, int B, int rows, hipStream_t s) {
+hipError_t gemm(const PlanOptions& o, const float* in, int K, const float* W, int ld, const float* bias, int N, float* out, int B, int rows, hipStream_t s) {
     ConvArgs a{};
     a.ntaps = 1;
     a.B = B;
@@ -52,10 +52,10 @@ hipError_t gemm(const float* in, int K, const float* W, int ld, const float* bia
     a.Cmain = K;
     a.seg_src = SegInfo{rows, rows, rows};
     a.seg_out = a.seg_src;
-    ConvTile t = conv_pick_tile(B, rows, N, K / 16, K, false);
+    ConvTile t = conv_pick_tile(o, B, rows, N, K / 16, K, false);
     t.KS = 1;                                  // (no slab: this operator owns no split-K workspace)
     while (t.NW > K / 16) t.NW /= 2;
-    return launch_conv(a, t, s);
+    return launch_conv(a, t, o, s);
 }
 }  // namespace
 
@@ -119,8 +119,8 @@ int mtv_xattn_forward(mtv_ctx* c, const float* x, const float* context, const un
     if (n_queries < 1 || n_queries > X.f.max_queries || n_keys < 1 || n_keys > X.f.max_keys) return fail(MTV_ERR_STATE, "token count outside the context's capacity");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(gemm(x, X.f.query_dim, X.Wq, X.ldq, X.zero, inner, X.q, batch, n_queries, s));
-    HIPCHK(gemm(context, X.f.context_dim, X.Wkv, X.ldkv, X.zero, 2 * inner, X.kv, batch, n_keys, s));
+    HIPCHK(gemm(c->opt, x, X.f.query_dim, X.Wq, X.ldq, X.zero, inner, X.q, batch, n_queries, s));
+    HIPCHK(gemm(c->opt, context, X.f.context_dim, X.Wkv, X.ldkv, X.zero, 2 * inner, X.kv, batch, n_keys, s));
     AttnArgs t{};
     t.qkv = X.q;
     t.kv = X.kv;
@@ -135,8 +135,8 @@ int mtv_xattn_forward(mtv_ctx* c, const float* x, const float* context, const un
     t.seg_start[0] = 0;
     t.seg_len[0] = n_queries;
     t.scale = 1.0f / std::sqrt(std::sqrt((float)X.f.dim_head));      // sim * d^-1/2 (unet.py:449), split evenly over q and k
-    HIPCHK(launch_attention(t, s));
-    HIPCHK(gemm(X.att, inner, X.Wo, X.ldo, X.bo, X.f.query_dim, out, batch, n_queries, s));
+    HIPCHK(launch_attention(t, c->opt, s));
+    HIPCHK(gemm(c->opt, X.att, inner, X.Wo, X.ldo, X.bo, X.f.query_dim, out, batch, n_queries, s));
     return MTV_OK;
 }
 

@@ -1,6 +1,6 @@
 """k_conv_win on its packed 3x3 weights (csrc/deep.hip, ConvArgs::Wwin: the conv matrix rewritten per (column tile, K slice, wave) in the order the K loop
 consumes it) against the same kernel on the legacy [krow][ldw] matrix: same MFMA order, same sums -- the outputs must be bit-equal.  MTV_WIN_PACKED=0 is
-read when a plan is built, so one process holds a plan of each form."""
+read when a context is created (a module's first forward), so one process holds a context of each form."""
 import os
 import re
 

@@ -26,8 +26,9 @@ def _dev():
 
 
 # The recipe-filled parameter values of a (config, seed) are computed ONCE per session (the arithmetic filler walks 132 M scalars for
-# the base net); every test still gets its OWN module and its own library context -- the mtv_debug_force_* knobs act on plans built
-# after the call, so a context must never be shared across tests.
+# the base net); every test still gets its OWN module and its own library context -- the mtv_debug_* knobs and the MTV_* environment are
+# read once, when a context is created (at the module's first forward), and that context keeps them for life: a test sets its knob
+# BEFORE it builds its net, and a context is never shared across tests.
 _FILLED = {}
 
 
@@ -518,7 +519,7 @@ def test_deep_levels_are_on_by_default_and_off_keeps_the_k_conv_path_green():
 
 @pytest.mark.parametrize("mask", [8, 32, 64, 80])      # (16 alone: test_deep_levels_are_on_by_default...; each bit once + round 4's whole plan)
 def test_deep_level_dataflow_variants_vs_reference_golden(mask):
-    """include/mtv_hip.h MTV_DEEP_OPT_*: k_attention + proj conv instead of the fused kernel (8), the three-launch attention block
+    """include/mtv_hip_debug.h MTV_DEEP_OPT_*: k_attention + proj conv instead of the fused kernel (8), the three-launch attention block
     everywhere (16), the one-launch k_deep_block everywhere (32: also the [128 x 512] blocks the default leaves on three launches), k_deep_finalize passes instead of the
     default completion by tagged granules inside the producing kernel (64; 80 = round 4's plan: 64 + 16) -- eps at three timesteps and a
     4-step sample vs the reference golden, and repeated forwards bit-equal (the arrival order of K slices / cluster workgroups must not

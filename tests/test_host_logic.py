@@ -86,10 +86,14 @@ def test_ddim_step_table_matches_reference_arithmetic():
 
 
 def test_library_loads_and_exports_every_declared_symbol():
-    """Every function include/mtv_hip.h declares is exported (no compute call: no GPU here)."""
-    hdr = open(os.path.join(ROOT, "include", "mtv_hip.h")).read()
-    declared = set(re.findall(r"\b(mtv_[a-z_0-9]+)\s*\(", hdr))
-    declared -= {"mtv_config", "mtv_ctx", "mtv_ddim_step", "mtv_work", "mtv_op_time"}
+    """Every function include/mtv_hip.h and include/mtv_hip_debug.h declare is exported (no compute call: no GPU here); the product header
+    declares no testing aid."""
+    names = lambda h: set(re.findall(r"\b(mtv_[a-z_0-9]+)\s*\(", open(os.path.join(ROOT, "include", h)).read()))
+    product, debug = names("mtv_hip.h"), names("mtv_hip_debug.h")
+    assert not [n for n in product if n.startswith(("mtv_debug_", "mtv_selftest_"))], "testing aids belong in mtv_hip_debug.h"
+    assert product - {"mtv_config", "mtv_ctx", "mtv_ddim_step", "mtv_work", "mtv_op_time"} == {name for name, _, _ in _lib.PRODUCT_SYMBOLS}
+    assert debug == {name for name, _, _ in _lib.DEBUG_SYMBOLS}, debug ^ {name for name, _, _ in _lib.DEBUG_SYMBOLS}
+    declared = (product | debug) - {"mtv_config", "mtv_ctx", "mtv_ddim_step", "mtv_work", "mtv_op_time"}
     lib = _lib.load()
     bound = {name for name, _, _ in _lib.SYMBOLS}
     assert declared == bound, (declared ^ bound)
@@ -285,7 +289,7 @@ def test_window_staged_conv_window_covers_every_tap(R, T, levels):
 
 
 def test_retired_deep_option_bits_are_rejected():
-    """include/mtv_hip.h, mtv_debug_deep_options: bits 1, 2 and 4 named dataflow variants that are retired -- a mask that carries one of
+    """include/mtv_hip_debug.h, mtv_debug_deep_options: bits 1, 2 and 4 named dataflow variants that are retired -- a mask that carries one of
     them is an error, never silently the default plan; the surviving bits (8, 16, 32, 64) and -1 are accepted (host only)."""
     lib = _lib.load()
     try:

@@ -1,6 +1,7 @@
 // Isolated benchmark of k_conv on one shape: sweeps tile shapes and ablations.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics conv_bench.hip -o conv_bench
 //   conv_bench Lout N Cin ntaps gn(0/1) [MT NT NW KS]...
+// (launchers get a default PlanOptions{}: the MTV_* environment does not steer this program -- set a field of the record here for an A/B)
 #include "../../moditalker_amd/csrc/conv.hip"
 #include <vector>
 #include <cstring>
@@ -66,10 +67,10 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     auto run = [&](ConvTile t) {
         const int reps = 20;
-        for (int i = 0; i < 3; ++i) CK(launch_conv(a, t, 0));
+        for (int i = 0; i < 3; ++i) CK(launch_conv(a, t, PlanOptions{}, 0));
         CK(hipDeviceSynchronize());
         CK(hipEventRecord(e0));
-        for (int i = 0; i < reps; ++i) CK(launch_conv(a, t, 0));
+        for (int i = 0; i < reps; ++i) CK(launch_conv(a, t, PlanOptions{}, 0));
         CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         const double us = ms * 1e3 / reps;
@@ -93,7 +94,7 @@ int main(int argc, char** argv) {
         for (int i = 7; i + 4 < argc; i += 5) run(ConvTile{atoi(argv[i]), atoi(argv[i + 1]), atoi(argv[i + 2]), atoi(argv[i + 3]), atoi(argv[i + 4])});
     } else {
         const int nchunks = ntaps * Cin / 16;
-        ConvTile p = conv_pick_tile(1, L, N, nchunks, Cin, gn);
+        ConvTile p = conv_pick_tile(PlanOptions{}, 1, L, N, nchunks, Cin, gn);
         printf("  picked:"); run(p);
         static const int cand[][2] = {{4, 4}, {2, 4}, {1, 4}, {2, 2}, {1, 2}};
         for (auto& c : cand) for (int NW : {1, 2, 4, 8}) for (int KS : {1, 2, 4, 8}) {

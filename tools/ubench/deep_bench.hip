@@ -5,6 +5,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics deep_bench.hip -o deep_bench
 //   deep_bench check          correctness cases
 //   deep_bench chain [nops] [r t]   timing (default 40 ops = 377 MB of weights: larger than the 256 MB Infinity Cache; r t = 4 2)
+// (launchers get a default PlanOptions{}: the MTV_* environment does not steer this program -- set a field of the record here for an A/B)
 #include "../../moditalker_amd/csrc/conv.hip"
 #include "../../moditalker_amd/csrc/deep.hip"
 #include "../../moditalker_amd/csrc/block.hip"
@@ -100,7 +101,7 @@ static int run_case(const Case& c) {
         a.rowtab = dt;
     }
     CK(hipMemset(out, 0xFF, (size_t)c.KS * c.B * L * c.N * 4));        // poison: NaN wherever nothing is written
-    CK(launch_deep_conv(a, tl, 0));
+    CK(launch_deep_conv(a, tl, PlanOptions{}, 0));
     CK(hipDeviceSynchronize());
     std::vector<float> got((size_t)c.KS * c.B * L * c.N);
     CK(hipMemcpy(got.data(), out, got.size() * 4, hipMemcpyDeviceToHost));
@@ -283,7 +284,7 @@ static void do_chain(int nops, int r, int t, int ks_arg, int nrg_arg) {
     }
     const double t_old = time_graph("k_conv chain (product tile)", [&]() {
         CK(hipMemsetAsync(sites + 192, 0, (size_t)((nops + 1) * STAT_COPIES * 192 - 192) * 8, s));     // (one memset per chain: the product zeroes in the head conv)
-        for (int o = 0; o < nops; ++o) CK(launch_conv(ca[o], tile, s));
+        for (int o = 0; o < nops; ++o) CK(launch_conv(ca[o], tile, PlanOptions{}, s));
     }, 30);
     // ---- deep chain
     std::vector<DeepArgs> da(nops);
@@ -323,7 +324,7 @@ static void do_chain(int nops, int r, int t, int ks_arg, int nrg_arg) {
         CK(hipMemcpy(slabs[0], x.data(), x.size() * 4, hipMemcpyHostToDevice));
         CK(hipMemcpy(actA[0], x.data(), x.size() * 4, hipMemcpyHostToDevice));
         CK(hipMemsetAsync(sites + 192, 0, (size_t)((nops + 1) * STAT_COPIES * 192 - 192) * 8, s));
-        for (int o = 0; o < 2; ++o) { CK(launch_conv(ca[o], tile, s)); CK(launch_deep_conv(da[o], tl, s)); }
+        for (int o = 0; o < 2; ++o) { CK(launch_conv(ca[o], tile, PlanOptions{}, s)); CK(launch_deep_conv(da[o], tl, PlanOptions{}, s)); }
         CK(hipStreamSynchronize(s));
         std::vector<float> a1((size_t)L * C), a2((size_t)KS * L * C);
         CK(hipMemcpy(a1.data(), actA[0], a1.size() * 4, hipMemcpyDeviceToHost));
@@ -339,7 +340,7 @@ static void do_chain(int nops, int r, int t, int ks_arg, int nrg_arg) {
         CK(hipMemcpy(slabs[0], x.data(), x.size() * 4, hipMemcpyHostToDevice));
         CK(hipMemcpy(actA[0], x.data(), x.size() * 4, hipMemcpyHostToDevice));
     }
-    const double t_new = time_graph("k_deep_conv chain", [&]() { for (int o = 0; o < nops; ++o) CK(launch_deep_conv(da[o], tl, s)); }, 30);
+    const double t_new = time_graph("k_deep_conv chain", [&]() { for (int o = 0; o < nops; ++o) CK(launch_deep_conv(da[o], tl, PlanOptions{}, s)); }, 30);
     printf("  ratio k_conv / k_deep_conv = %.2fx\n", t_old / t_new);
 #ifdef MTV_DEEP_STAMP
     {
@@ -398,7 +399,7 @@ static int run_attn(int r, int t, int C, int H, int whole, int res_ks, bool timi
     }
     a.form = form;
     a.res = make_src(B, L, C, res_ks, xr);
-    if (!deep_attn_configure(a)) { printf("attn L%d d%d: not configurable\n", L, d); return 1; }
+    if (!deep_attn_configure(a, PlanOptions{})) { printf("attn L%d d%d: not configurable\n", L, d); return 1; }
     const size_t LC = (size_t)L * C, slab = (size_t)B * LC;
     float* out = dnew<float>((size_t)8 * slab);
     a.out = out; a.out_slab_stride = (unsigned)slab;
@@ -525,7 +526,7 @@ static int do_attn128(bool timing) {
         DeepAttnArgs a{};
         a.B = 1; a.L = 128; a.C = 1024; a.H = 8; a.r = 8; a.t = 4; a.whole = 1;
         a.Wpk = reinterpret_cast<const float*>(&a);             // (configure only asks whether a packed copy exists)
-        if (deep_attn_configure(a)) printf("product shape [128 x 1024] d128: the rule picks HPW%d NC%d -> %d slabs, %d workgroups\n", a.HPW, a.NC, a.nhg, a.ncg * a.B * a.nqg * a.nhg);
+        if (deep_attn_configure(a, PlanOptions{})) printf("product shape [128 x 1024] d128: the rule picks HPW%d NC%d -> %d slabs, %d workgroups\n", a.HPW, a.NC, a.nhg, a.ncg * a.B * a.nqg * a.nhg);
         else { printf("product shape [128 x 1024] d128: not configurable\n"); ++bad; }
     }
     printf("%s (%d failing)\n", bad ? "ATTN128 CHECK FAILED" : "ATTN128 CHECK OK", bad);
@@ -769,7 +770,7 @@ static void do_win(int nops, int r, int t, int C) {
         hipGraph_t gr; hipGraphExec_t ge;
         CK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         CK(hipMemsetAsync(sites + 192, 0, (size_t)((nops + 1) * STAT_COPIES * 192 - 192) * 8, s));
-        for (int o = 0; o < nops; ++o) CK(launch_conv(ca[o], tile, s));
+        for (int o = 0; o < nops; ++o) CK(launch_conv(ca[o], tile, PlanOptions{}, s));
         CK(hipStreamEndCapture(s, &gr));
         CK(hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0));
         CK(hipGraphLaunch(ge, s));
@@ -867,7 +868,7 @@ static void do_pw(int r, int t, int K, int N) {
         if (tile.NW != 96 && (conv_smem_bytes(a, tile) > 120 * 1024 || tile.NW * tile.KS > K / 16)) return;
         hipGraph_t gr; hipGraphExec_t ge;
         CK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        for (int o = 0; o < nops; ++o) CK(launch_conv(a, tile, s));
+        for (int o = 0; o < nops; ++o) CK(launch_conv(a, tile, PlanOptions{}, s));
         CK(hipStreamEndCapture(s, &gr));
         CK(hipGraphInstantiate(&ge, gr, nullptr, nullptr, 0));
         CK(hipGraphLaunch(ge, s));
