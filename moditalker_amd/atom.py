@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._context import HipContextMixin
 from .ddpm import ddim_step_table, ddim_time_pairs
 
 NFEATS = 204                      # 68 landmarks x 3; forward() splits them 0:17 | 17:48 | 48:68
@@ -95,8 +96,10 @@ class _Stack(nn.Module):
         self.stack = nn.ModuleList(layers)
 
 
-class MotionDecoder(nn.Module):
+class MotionDecoder(HipContextMixin, nn.Module):
     """Same constructor kwargs and state_dict as the reference's MotionDecoder; forward / guided_forward run on the HIP library."""
+
+    _destroy = "mtv_atom_destroy"
 
     def __init__(self, nfeats: int, seq_len: int = 150, latent_dim: int = 256, ff_size: int = 1024, num_layers: int = 4,
                  num_heads: int = 4, dropout: float = 0.1, cond_feature_dim: int = 1024, activation=None, use_rotary=True,
@@ -140,26 +143,6 @@ class MotionDecoder(nn.Module):
         self._key = None
         self._fingerprint = None
 
-    # ---- context life cycle (as the other classes)
-    def _release(self):
-        if getattr(self, "_ctx", None) is not None:
-            _lib.load().mtv_atom_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def __getstate__(self):
-        st = dict(self.__dict__)
-        st["_ctx"], st["_key"], st["_fingerprint"] = None, None, None
-        return st
-
-    def invalidate_weights(self):
-        self._fingerprint = None
-
     def tables(self):
         """(rot [3 L + 2, D / 2, 2] cos | sin, time_freqs [D / 2]) in fp32 on the CPU, evaluated as the reference does:
         position.float() * freqs (rotary_embedding_torch.py:117-132) and exp(arange * -log(10000) / (half - 1)) (utils.py:41-48)."""
@@ -186,18 +169,10 @@ class MotionDecoder(nn.Module):
                 ctx = C.c_void_p()
                 _lib.check(lib.mtv_atom_create(C.byref(cfg), C.byref(ctx)), "mtv_atom_create")
             self._ctx, self._key, self._fingerprint = ctx, (device, cap), None
-        fp = tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
+        fp = self._weights_fingerprint()
         if fp != self._fingerprint:
-            torch.cuda.synchronize(device)
-            sd = self.state_dict()
+            self._upload_weights(self._ctx, device)
             with torch.cuda.device(device):
-                key = C.create_string_buffer(256)
-                for i in range(lib.mtv_num_weights(self._ctx)):       # the context lists the keys its forward reads
-                    _lib.check(lib.mtv_weight_info(self._ctx, i, key, 256, None, None), "mtv_weight_info")
-                    k = key.value.decode()
-                    t = sd[k].detach().to(device="cpu", dtype=torch.float32).contiguous()
-                    shp = (C.c_int64 * t.dim())(*t.shape)
-                    _lib.check(lib.mtv_load_weight(self._ctx, k.encode(), C.c_void_p(t.data_ptr()), t.dim(), shp), f"mtv_load_weight({k})")
                 rot, tf = self.tables()
                 _lib.check(lib.mtv_atom_set_tables(self._ctx, C.c_void_p(rot.data_ptr()), rot.shape[0], C.c_void_p(tf.data_ptr())),
                            "mtv_atom_set_tables")

@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._context import HipContextMixin
 
 HEADS, DIM_HEAD, DEPTH = 8, 64, 8        # vit_modules.py:162-163,243-244; autoencoder_vit.py:110-116
 
@@ -86,7 +87,10 @@ class _QuantTransformer(nn.Module):
             for _ in range(depth)])
 
 
-class ViTAutoencoder(nn.Module):
+class ViTAutoencoder(HipContextMixin, nn.Module):
+    _destroy = "mtv_ae_destroy"
+    _transient = {"_ctx": None, "_ctx_device": None, "_ctx_batch": 0, "_fingerprint": None}
+
     def __init__(self, embed_dim, ddconfig, ckpt_path=None, ignore_keys=[], image_key="image", colorize_nlabels=None,
                  monitor=None, max_batch: int = 1):
         super().__init__()
@@ -154,25 +158,6 @@ class ViTAutoencoder(nn.Module):
         return time_tab, space_tab
 
     # ------------------------------------------------------------------ HIP context management
-    def _release(self):
-        if getattr(self, "_ctx", None) is not None:
-            _lib.load().mtv_ae_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def __getstate__(self):
-        st = dict(self.__dict__)
-        st["_ctx"], st["_ctx_device"], st["_ctx_batch"], st["_fingerprint"] = None, None, 0, None
-        return st
-
-    def invalidate_weights(self):
-        self._fingerprint = None
-
     def load_state_dict(self, *a, **k):
         r = super().load_state_dict(*a, **k)
         self._fingerprint = None
@@ -196,31 +181,12 @@ class ViTAutoencoder(nn.Module):
                 _lib.check(lib.mtv_ae_create(C.byref(cfg), C.byref(ctx)), "mtv_ae_create")
             self._ctx, self._ctx_device, self._ctx_batch = ctx, device, max(batch, self.max_batch)
             self._fingerprint = None
-        fp = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        fp = self._weights_fingerprint()
         if fp != self._fingerprint:
-            sd = self.state_dict()
-            key = C.create_string_buffer(256)
-            ndim = C.c_int()
-            shape = (C.c_int64 * 4)()
-            torch.cuda.synchronize(device)
+            self._upload_weights(self._ctx, device)
+            tt, st = self._rotary_tables()
             with torch.cuda.device(device):
-                for i in range(lib.mtv_num_weights(self._ctx)):
-                    _lib.check(lib.mtv_weight_info(self._ctx, i, key, 256, C.byref(ndim), shape), "mtv_weight_info")
-                    k = key.value.decode()
-                    if k not in sd:
-                        raise _lib.MtvError(f"library expects weight '{k}' which this module does not hold")
-                    t = sd[k].detach().to(device=device, dtype=torch.float32).contiguous()
-                    if t.data_ptr() != sd[k].data_ptr():
-                        # a converted / copied temporary is produced on torch's CURRENT stream, while mtv_load_weight copies and
-                        # repacks on the NULL stream: finish producing it first (it stays referenced until the call returns,
-                        # and the call returns only after its own copy + repack have run)
-                        torch.cuda.current_stream(device).synchronize()
-                    shp = (C.c_int64 * t.dim())(*t.shape)
-                    _lib.check(lib.mtv_load_weight(self._ctx, k.encode(), C.c_void_p(t.data_ptr()), t.dim(), shp), f"mtv_load_weight({k})")
-                tt, st = self._rotary_tables()
                 _lib.check(lib.mtv_ae_set_rotary(self._ctx, C.c_void_p(tt.data_ptr()), C.c_void_p(st.data_ptr())), "mtv_ae_set_rotary")
-            if lib.mtv_weights_missing(self._ctx):
-                raise _lib.MtvError(f"{lib.mtv_weights_missing(self._ctx)} weights missing after upload")
             self._fingerprint = fp
         return self._ctx
 

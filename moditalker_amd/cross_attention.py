@@ -15,9 +15,12 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._context import HipContextMixin
 
 
-class CrossAttention(nn.Module):
+class CrossAttention(HipContextMixin, nn.Module):
+    _destroy = "mtv_xattn_destroy"
+
     def __init__(self, query_dim, context_dim=None, heads=8, dim_head=64, dropout=0.0):
         super().__init__()
         inner_dim = dim_head * heads
@@ -35,25 +38,6 @@ class CrossAttention(nn.Module):
         self._key = None
         self._fingerprint = None
 
-    def _release(self):
-        if getattr(self, "_ctx", None) is not None:
-            _lib.load().mtv_xattn_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def __getstate__(self):
-        st = dict(self.__dict__)
-        st["_ctx"], st["_key"], st["_fingerprint"] = None, None, None
-        return st
-
-    def invalidate_weights(self):
-        self._fingerprint = None
-
     def _context(self, device, B, N, M):
         if device.type != "cuda":
             raise _lib.MtvError("CrossAttention runs only on a HIP device (tensor is on %s); there is no CPU fallback" % device)
@@ -66,19 +50,9 @@ class CrossAttention(nn.Module):
                 ctx = C.c_void_p()
                 _lib.check(lib.mtv_xattn_create(C.byref(cfg), C.byref(ctx)), "mtv_xattn_create")
             self._ctx, self._key, self._fingerprint = ctx, key, None
-        fp = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        fp = self._weights_fingerprint()
         if fp != self._fingerprint:
-            torch.cuda.synchronize(device)
-            with torch.cuda.device(device):
-                for k, v in self.state_dict().items():
-                    t = v.detach().to(device=device, dtype=torch.float32).contiguous()
-                    if t.data_ptr() != v.data_ptr():
-                        # a converted / copied temporary is produced on torch's CURRENT stream, while mtv_load_weight copies and
-                        # repacks on the NULL stream: finish producing it first (it stays referenced until the call returns,
-                        # and the call returns only after its own copy + repack have run)
-                        torch.cuda.current_stream(device).synchronize()
-                    shp = (C.c_int64 * t.dim())(*t.shape)
-                    _lib.check(lib.mtv_load_weight(self._ctx, k.encode(), C.c_void_p(t.data_ptr()), t.dim(), shp), f"mtv_load_weight({k})")
+            self._upload_weights(self._ctx, device)
             self._fingerprint = fp
         return self._ctx
 

@@ -14,10 +14,9 @@
 //     to_out GEMM gathers back ((f, n) <- (n, f)) while adding the residual in the natural order;
 //   * the quant stacks read per-plane sequences + a learned token through a gather kernel.
 #include "plan_internal.h"
+#include "tok_common.h"
 
 namespace mtv {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------
 // weight repacking
@@ -48,6 +47,7 @@ hipError_t launch_repeat(const float* src, float* dst, int n, int rep, hipStream
 // ---------------------------------------------------------------------------------------------
 // LayerNorm over the channel axis (PreNorm, vit_modules.py:70-79 / autoencoder_vit.py:15-23): one wave per token,
 // two-pass fp32 (mean, then centred sum of squares) like ATen's layer_norm; eps = 1e-5
+// (not tok_common.h's ln_row_stats: the row stays in registers and is summed pairwise with fmaf, another summation order)
 // ---------------------------------------------------------------------------------------------
 template <int VPL>   // float4 per lane: C = 256 * VPL ... handled generally below
 __global__ __launch_bounds__(256) void k_layernorm(const float* x, const float* gamma, const float* beta, float* out, long ntok, int C) {
@@ -135,7 +135,6 @@ static hipError_t launch_rotary(float* qkv, const float* tab, long ntok, int H, 
 
 // GEGLU (vit_modules.py:88-91): out[t][c] = h[t][c] * gelu(h[t][half + c]), exact (erf) GELU like F.gelu's default;
 // mode 1: plain GELU (autoencoder_vit.py:26-32 FeedForward of the quant stacks): out[t][c] = gelu(h[t][c])
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __global__ __launch_bounds__(256) void k_geglu(const float* h, float* out, long ntok, int half, int plain) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int q4 = half / 4;
@@ -695,36 +694,7 @@ int mtv_ae_profile(mtv_ctx* c, int batch, int extract, int iters, mtv_op_time* o
     Plan* p = nullptr;
     if ((rc = get_ae_plan(c, *cf, batch, extract ? MODE_AE_EXTRACT : MODE_AE_DECODE, &p)) != MTV_OK) return rc;
     if ((rc = autotune(c, p, s)) != MTV_OK) return rc;
-    const int n = (int)p->ops.size();
-    *n_out = n;
-    if (!out) return MTV_OK;
-    if (cap < n) return fail(MTV_ERR_INVALID, "profile table too small");
-    std::vector<hipEvent_t> ev((size_t)n + 1);
-    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-    std::vector<double> acc(n, 0.0);
-    for (int itr = 0; itr < iters; ++itr) {
-        HIPCHK(hipEventRecord(ev[0], s));
-        for (int i = 0; i < n; ++i) {
-            hipError_t e = p->ops[i].run(s);
-            if (e != hipSuccess) return fail(MTV_ERR_HIP, "launch " + p->ops[i].name + ": " + hipGetErrorString(e));
-            HIPCHK(hipEventRecord(ev[i + 1], s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-        for (int i = 0; i < n; ++i) {
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-            acc[i] += ms;
-        }
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    for (int i = 0; i < n; ++i) {
-        std::memset(&out[i], 0, sizeof(mtv_op_time));
-        std::strncpy(out[i].name, p->ops[i].name.c_str(), sizeof(out[i].name) - 1);
-        out[i].ms = (float)(acc[i] / iters);
-        out[i].flops = p->ops[i].flops;
-        out[i].bytes = p->ops[i].bytes;
-    }
-    return MTV_OK;
+    return profile_ops(c, p->ops, iters, out, cap, n_out, s);
 }
 
 }  // extern "C"

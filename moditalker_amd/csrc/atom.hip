@@ -19,17 +19,15 @@
 //     not write the buffer it reads, so the sample has two buffers and even / odd steps are two graphs (x_io -> x_alt, x_alt -> x_io).
 //
 // Kernels: k_tok_linear (LayerNorm + rotary prologue, exact-f32 MFMA GEMM against [N][K] weights as the checkpoint stores them, bias /
-// GELU / Mish / SiLU / FiLM / residual / guidance epilogues) and k_atom_attn (softmax attention of one head for 16 queries; any query
-// and key length up to ATT_KMAX keys, tails masked by loop bounds).  Reference quirks that are behaviour are kept: see atom_build_step.
+// GELU / Mish / SiLU / FiLM / residual / guidance epilogues) and tok_attn.hip's k_tok_attn<512> (softmax attention of one head for 16
+// queries, shared with hubert.hip; every key of a clip is in its one chunk).  Reference quirks that are behaviour are kept: see atom_build_step.
 #include "plan_internal.h"
+#include "tok_common.h"
 
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int ATT_KMAX = 512;      // keys one k_atom_attn workgroup holds scores for (memory has 3 L + 2 keys: L <= 170)
+constexpr int ATT_KMAX = 512;      // keys per chunk of k_tok_attn here; create refuses more, so a workgroup sees one chunk (memory has 3 L + 2 keys: L <= 170)
 constexpr int NFEAT = 204;         // 68 landmarks x 3 (model.py:402-410 hard-wires the 17 | 31 | 20 split)
 
-enum { ACT_NONE = 0, ACT_GELU = 1, ACT_MISH = 2, ACT_SILU = 3 };
 enum { EPI_PLAIN = 0, EPI_RES = 1, EPI_FILM_RES = 2, EPI_FILM_SELF = 3, EPI_GUIDE = 4 };
 
 struct AtomCur {                   // device record the guided final_layer epilogue reads (graph kernel arguments are frozen, this is not)
@@ -70,21 +68,10 @@ struct TokLinArgs {
     int stitch_L;                  // long sampler: clip length L (even); 0: no stitch
 };
 
-__device__ __forceinline__ float act_apply(float y, int act) {
-    if (act == ACT_GELU) return 0.5f * y * (1.0f + erff(y * 0.70710678118654752440f));
-    if (act == ACT_MISH) return y * tanhf(y > 20.0f ? y : log1pf(expf(y)));
-    if (act == ACT_SILU) return y / (1.0f + expf(-y));
-    return y;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // 32 rows x 32 columns per workgroup; the four waves take the 16-wide K chunks round robin and meet in LDS (fixed order: results do not
 // depend on the grid).  Lane (j, q) of a wave loads A[row j][16 c + 4 q ..+3] and W[col j][16 c + 4 q ..+3] as one 16-byte load each; the
 // four MFMA steps of a chunk pair element i of both, so the K order inside a chunk is a permutation shared by A and B.
+// (not hubert.hip's k_hub_gemm, where every wave walks all of K: the bits and the tile shapes differ by design)
 template <int HALVES>
 __global__ __launch_bounds__(256) void k_tok_linear(const TokLinArgs a) {
     __shared__ float s_stat[HALVES][32][2];
@@ -102,15 +89,7 @@ __global__ __launch_bounds__(256) void k_tok_linear(const TokLinArgs a) {
             float mean = 0.0f, rstd = 0.0f;
             if (r < a.M) {
                 const size_t ro = (in_row(r) + (size_t)h * a.half_rows) * a.lda;
-                float s = 0.0f;
-                for (int k = lane; k < a.K; k += 64) s += a.A[ro + k] + (a.A2 ? a.A2[ro + k] : 0.0f);
-                mean = wave_sum(s) / (float)a.K;
-                float v = 0.0f;
-                for (int k = lane; k < a.K; k += 64) {
-                    const float d = a.A[ro + k] + (a.A2 ? a.A2[ro + k] : 0.0f) - mean;
-                    v += d * d;
-                }
-                rstd = 1.0f / sqrtf(wave_sum(v) / (float)a.K + 1e-5f);
+                ln_row_stats(a.A, a.A2, ro, a.K, 1e-5f, lane, &mean, &rstd);
             }
             if (lane == 0) {
                 s_stat[h][rr][0] = mean;
@@ -256,91 +235,6 @@ hipError_t launch_tok_linear(const TokLinArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// nn.MultiheadAttention's core for one (clip, stream, head, 16 queries): softmax(q k^T / sqrt(d)) v.  Channels of a head are h d .. h d + d - 1
-// of the q, k and v rows.  Scores of the 16 queries against ALL keys sit in LDS (Lk <= ATT_KMAX); every loop is bounded by Lq / Lk.
-struct AtomAttnArgs {
-    const float *q, *k, *v;
-    float* o;
-    long long q_bs, k_bs, o_bs;    // floats between clips
-    int q_rs, k_rs, o_rs;          // floats between tokens
-    int q_ss, k_ss, o_ss;          // floats between the interleaved streams of a clip (S = 2: lip | face rows of one token)
-    int Lq, Lk, H, d, S;
-    float scale;
-};
-__global__ __launch_bounds__(256) void k_atom_attn(const AtomAttnArgs a) {
-    __shared__ float s_q[16][68];
-    __shared__ float s_p[16][ATT_KMAX];
-    __shared__ float s_inv[16];
-    const int tid = threadIdx.x, h = blockIdx.y, bz = blockIdx.z, b = bz / a.S, st = bz - b * a.S;
-    const int q0 = blockIdx.x * 16;
-    const float* qb = a.q + (size_t)b * a.q_bs + (size_t)st * a.q_ss + h * a.d;
-    const float* kb = a.k + (size_t)b * a.k_bs + (size_t)st * a.k_ss + h * a.d;
-    const float* vb = a.v + (size_t)b * a.k_bs + (size_t)st * a.k_ss + h * a.d;
-    {
-        const int qi = tid >> 4, d4 = (tid & 15) * 4;
-        if (d4 < a.d) {
-            f32x4 x{0.0f, 0.0f, 0.0f, 0.0f};
-            if (q0 + qi < a.Lq) x = *reinterpret_cast<const f32x4*>(qb + (size_t)(q0 + qi) * a.q_rs + d4) * a.scale;
-            *reinterpret_cast<f32x4*>(&s_q[qi][d4]) = x;
-        }
-    }
-    __syncthreads();
-    {   // scores: thread = (key, group of 4 queries)
-        const int g = tid & 3;
-        for (int kj = tid >> 2; kj < a.Lk; kj += 64) {
-            const float* kr = kb + (size_t)kj * a.k_rs;
-            float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-            for (int dd = 0; dd < a.d; dd += 4) {
-                const f32x4 kv = *reinterpret_cast<const f32x4*>(kr + dd);
-                const f32x4 q0v = *reinterpret_cast<const f32x4*>(&s_q[4 * g + 0][dd]), q1v = *reinterpret_cast<const f32x4*>(&s_q[4 * g + 1][dd]);
-                const f32x4 q2v = *reinterpret_cast<const f32x4*>(&s_q[4 * g + 2][dd]), q3v = *reinterpret_cast<const f32x4*>(&s_q[4 * g + 3][dd]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    s0 = fmaf(q0v[i], kv[i], s0);
-                    s1 = fmaf(q1v[i], kv[i], s1);
-                    s2 = fmaf(q2v[i], kv[i], s2);
-                    s3 = fmaf(q3v[i], kv[i], s3);
-                }
-            }
-            s_p[4 * g + 0][kj] = s0;
-            s_p[4 * g + 1][kj] = s1;
-            s_p[4 * g + 2][kj] = s2;
-            s_p[4 * g + 3][kj] = s3;
-        }
-    }
-    __syncthreads();
-    {   // softmax: a wave per 4 rows
-        const int wave = tid >> 6, lane = tid & 63;
-        for (int qi = wave * 4; qi < wave * 4 + 4; ++qi) {
-            float m = -INFINITY;
-            for (int kj = lane; kj < a.Lk; kj += 64) m = fmaxf(m, s_p[qi][kj]);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-            float sum = 0.0f;
-            for (int kj = lane; kj < a.Lk; kj += 64) {
-                const float e = expf(s_p[qi][kj] - m);
-                s_p[qi][kj] = e;
-                sum += e;
-            }
-            sum = wave_sum(sum);
-            if (lane == 0) s_inv[qi] = 1.0f / sum;
-        }
-    }
-    __syncthreads();
-    {
-        const int qi = tid >> 4, d4 = (tid & 15) * 4;
-        if (d4 < a.d && q0 + qi < a.Lq) {
-            f32x4 acc{0.0f, 0.0f, 0.0f, 0.0f};
-            for (int kj = 0; kj < a.Lk; ++kj) acc += *reinterpret_cast<const f32x4*>(vb + (size_t)kj * a.k_rs + d4) * s_p[qi][kj];
-            *reinterpret_cast<f32x4*>(a.o + (size_t)b * a.o_bs + (size_t)st * a.o_ss + (size_t)(q0 + qi) * a.o_rs + h * a.d + d4) = acc * s_inv[qi];
-        }
-    }
-}
-hipError_t launch_atom_attn(const AtomAttnArgs& a, int nb, hipStream_t s) {
-    hipLaunchKernelGGL(k_atom_attn, dim3((unsigned)((a.Lq + 15) / 16), (unsigned)a.H, (unsigned)(nb * a.S)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
 // ---- small element-wise kernels
 // SinusoidalPosEmb (utils.py:36-48): [sin(t f_i) | cos(t f_i)], f from the host's table
 __global__ void k_atom_time_sin(const float* tv, const float* freqs, float* out, int nb, int half) {
@@ -365,13 +259,6 @@ __global__ void k_atom_advance(const DdimStep* steps, const float* gws, int* cou
     if (gws) cur->gw = gws[i];
     for (int b = 0; b < nb; ++b) tv[b] = (float)st.t;
     *counter = i + 1;
-}
-// dst[b][i] = src[b][i] for i < n (strides in floats; src_bs = 0 broadcasts one block to every clip)
-__global__ void k_atom_copy(const float* src, long long src_bs, float* dst, long long dst_bs, long long n, int nb) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n * nb) return;
-    const long long b = i / n, w = i - b * n;
-    dst[b * dst_bs + w] = src[b * src_bs + w];
 }
 __global__ void k_atom_mean(const float* src, float* dst, int nb, int T, int D) {      // mean over the T tokens of a clip
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -449,11 +336,6 @@ void with_rot(TokLinArgs& a, AtomState& A, int cols, int pos0 = 0) {
     a.rot_cols = cols;
     a.pos0 = pos0;
 }
-hipError_t copy_rows(const float* src, long long src_bs, float* dst, long long dst_bs, long long n, int nb, hipStream_t s) {
-    if (n * nb <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_atom_copy, dim3((unsigned)((n * nb + 255) / 256)), dim3(256), 0, s, src, src_bs, dst, dst_bs, n, nb);
-    return hipGetLastError();
-}
 
 // TransformerEncoderLayer (model.py:35-99, norm_first): x += sa(norm1 x); x += linear2(gelu(linear1(norm2 x))).  q and k see the rotated
 // normalised row, v the unrotated one (model.py:84-94).
@@ -469,7 +351,7 @@ hipError_t encoder_layer(AtomState& A, const std::string& pre, float* x, int nb,
     with_ln(a, A, pre + ".norm1");
     with_rot(a, A, 2 * D);
     ACHK(launch_tok_linear(a, s));
-    AtomAttnArgs t{};
+    TokAttnArgs t{};
     t.q = A.EQKV;
     t.k = A.EQKV + D;
     t.v = A.EQKV + 2 * D;
@@ -483,7 +365,7 @@ hipError_t encoder_layer(AtomState& A, const std::string& pre, float* x, int nb,
     t.d = D / A.f.num_heads;
     t.S = 1;
     t.scale = 1.0f / std::sqrt((float)t.d);
-    ACHK(launch_atom_attn(t, nb, s));
+    ACHK(launch_tok_attn(t, nb, ATT_KMAX, s));
     a = lin(A.EATT, D, M, D, A.w.at(pre + ".self_attn.out_proj.weight"), A.w.at(pre + ".self_attn.out_proj.bias"), D, x, D);
     a.epi = EPI_RES;
     a.res = x;
@@ -535,9 +417,9 @@ hipError_t atom_setup(AtomState& A, int B, int mode, const float* face, const fl
         ACHK(hidden_mlp(A, "non_attn_cond_projection", A.pool, A.ch + (size_t)kb0 * D, B, s));
     }
     if (nnull) {      // torch.where(keep_mask, tokens, null) with an all-false mask (model.py:429-430, 448-449, 458-459)
-        ACHK(copy_rows(A.w.at("null_cond_embed"), 0, A.CT, (long long)2 * L * D, (long long)2 * L * D, nnull, s));
-        ACHK(copy_rows(A.w.at("face_null_cond_embed"), 0, A.FT, (long long)L * D, (long long)L * D, nnull, s));
-        ACHK(copy_rows(A.w.at("null_cond_hidden"), 0, A.ch, D, D, nnull, s));
+        ACHK(launch_tok_copy(A.w.at("null_cond_embed"), 0, A.CT, (long long)2 * L * D, (long long)2 * L * D, nnull, s));
+        ACHK(launch_tok_copy(A.w.at("face_null_cond_embed"), 0, A.FT, (long long)L * D, (long long)L * D, nnull, s));
+        ACHK(launch_tok_copy(A.w.at("null_cond_hidden"), 0, A.ch, D, D, nnull, s));
     }
     hipLaunchKernelGGL(k_atom_mean, dim3((unsigned)((nb * D + 255) / 256)), dim3(256), 0, s, A.FT, A.pool, nb, L, D);
     ACHK(hipGetLastError());
@@ -545,9 +427,9 @@ hipError_t atom_setup(AtomState& A, int B, int mode, const float* face, const fl
     hipLaunchKernelGGL(k_atom_hid, dim3((unsigned)((nb * D + 255) / 256)), dim3(256), 0, s, A.fh, A.ch, A.hid_add, nb * D);
     ACHK(hipGetLastError());
     // c = cat(cond_tokens, t_tokens, face_tokens), face_wo_lip_c = cat(t_tokens, face_tokens) (model.py:461-466); the time rows stay zero here
-    ACHK(copy_rows(A.CT, (long long)2 * L * D, A.Cmem, (long long)Lm * D, (long long)2 * L * D, nb, s));
-    ACHK(copy_rows(A.FT, (long long)L * D, A.Cmem + (size_t)(2 * L + 2) * D, (long long)Lm * D, (long long)L * D, nb, s));
-    ACHK(copy_rows(A.FT, (long long)L * D, A.Cface + (size_t)2 * D, (long long)Lf * D, (long long)L * D, nb, s));
+    ACHK(launch_tok_copy(A.CT, (long long)2 * L * D, A.Cmem, (long long)Lm * D, (long long)2 * L * D, nb, s));
+    ACHK(launch_tok_copy(A.FT, (long long)L * D, A.Cmem + (size_t)(2 * L + 2) * D, (long long)Lm * D, (long long)L * D, nb, s));
+    ACHK(launch_tok_copy(A.FT, (long long)L * D, A.Cface + (size_t)2 * D, (long long)Lf * D, (long long)L * D, nb, s));
     for (int l = 0; l < A.nl; ++l) {      // keys (rotated norm_cond row) | values (unrotated) of both cross-attentions (model.py:212-223)
         const std::string pre = "seqTransDecoder.stack." + std::to_string(l) + ".multihead_attn.";
         const float *W = A.w.at(pre + "in_proj_weight") + (size_t)D * D, *bias = A.w.at(pre + "in_proj_bias") + D;
@@ -578,7 +460,7 @@ void atom_build_step(AtomState* Ap, Plan* p, int B, bool guided, bool sampler, f
     const int nb = guided ? 2 * B : B, M = nb * L;
     auto add = [&](const std::string& name, std::function<hipError_t(hipStream_t)> fn) { p->ops.push_back(Op{std::move(fn), name}); };
     auto add_lin = [&](const std::string& name, const TokLinArgs& a) { add(name, [a](hipStream_t s) { return launch_tok_linear(a, s); }); };
-    auto add_att = [&](const std::string& name, const AtomAttnArgs& t, int n) { add(name, [t, n](hipStream_t s) { return launch_atom_attn(t, n, s); }); };
+    auto add_att = [&](const std::string& name, const TokAttnArgs& t, int n) { add(name, [t, n](hipStream_t s) { return launch_tok_attn(t, n, ATT_KMAX, s); }); };
     if (sampler)
         add("advance", [Ap, nb, stitch](hipStream_t s) {
             hipLaunchKernelGGL(k_atom_advance, dim3(1), dim3(64), 0, s, Ap->steps, stitch ? Ap->gws : (const float*)nullptr, Ap->counter, Ap->cur, Ap->tv, nb);
@@ -629,7 +511,7 @@ void atom_build_step(AtomState* Ap, Plan* p, int B, bool guided, bool sampler, f
         with_ln(a, A, pre + "norm1");
         with_rot(a, A, 2 * D);
         add_lin(tag + "qkv1", a);
-        AtomAttnArgs t{};
+        TokAttnArgs t{};
         t.q = A.QKV;
         t.k = A.QKV + D;
         t.v = A.QKV + 2 * D;
@@ -666,7 +548,7 @@ void atom_build_step(AtomState* Ap, Plan* p, int B, bool guided, bool sampler, f
         with_ln(a, A, pre + "norm2");
         with_rot(a, A, D);
         add_lin(tag + "q2_lip", a);
-        t = AtomAttnArgs{};
+        t = TokAttnArgs{};
         t.q = A.QKV;
         t.k = A.QKV + D;
         t.v = A.QKV + 2 * D;
@@ -681,7 +563,7 @@ void atom_build_step(AtomState* Ap, Plan* p, int B, bool guided, bool sampler, f
         t.S = 1;
         t.scale = 1.0f / std::sqrt((float)d);
         add_att(tag + "attn2_face", t, nb);
-        AtomAttnArgs u = t;
+        TokAttnArgs u = t;
         u.q = Q;
         u.q_bs = (long long)L * D;
         u.q_rs = D;

@@ -13,29 +13,22 @@
 //     depends on its own row, its column and the weights only: neither the grid nor the batch size can change a bit.
 //   * optional LayerNorm prologue over K (Linears), bias / exact-erf GELU / residual epilogue.
 // LayerNorm + GELU of a conv layer is its own in-place pass (k_hub_ln, a wave per row): the next layer's GEMM row spans k tokens, each with
-// its own statistics.  Layer 1 (one input channel, K = 10) is k_hub_conv0.  Attention is k_hub_attn: 16 queries of one head per
-// workgroup, keys in chunks of 256 with a running max / sum (any key length: 1000 at a full 20 s clip), keys in index order.
+// its own statistics.  Layer 1 (one input channel, K = 10) is k_hub_conv0.  Attention is tok_attn.hip's k_tok_attn<256>, shared with
+// atom.hip: 16 queries of one head per workgroup, keys in chunks of 256 with a running max / sum (any key length: 1000 at a full 20 s
+// clip), keys in index order.
 // A forward is one linear chain of plain launches on the caller's stream; shapes follow the clip length, so nothing is captured.
 #include "plan_internal.h"
+#include "tok_common.h"
 
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-enum { HACT_NONE = 0, HACT_GELU = 1 };
-constexpr int HUB_KCH = 256;       // keys per chunk of k_hub_attn
+constexpr int HUB_KCH = 256;       // keys per chunk of k_tok_attn here
 constexpr int HUB_PARTS = 256;     // workgroups (= partial sums) of a normalisation pass
-
-__device__ __forceinline__ float hub_gelu(float y) { return 0.5f * y * (1.0f + erff(y * 0.70710678118654752440f)); }
-__device__ __forceinline__ float hub_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- the GEMM
 // Logical output row r: clip b = r / T_out, token t = r % T_out.  Reduction index k: tap = k / kc, channel kk = k % kc; the A element is
 // A[b a_bs + (t tok_step + tap - pad) tap_stride + g a_goff + kk], zero when that token is outside [0, T_in).  kc and K are multiples of 4,
 // so a lane's quad never straddles a tap.  Group g (blockIdx.z) owns weight rows / output columns g N .. g N + N - 1.
+// (not atom.hip's k_tok_linear, which splits K over the four waves and meets in LDS: the bits and the tile shapes differ by design)
 struct HubGemm {
     const float* A;
     long long a_bs;
@@ -60,18 +53,7 @@ __global__ __launch_bounds__(256) void k_hub_gemm(const HubGemm a) {
         for (int i = 0; i < 16; ++i) {
             const int rr = wave * 16 + i, r = m0 + rr;
             float mean = 0.0f, rstd = 0.0f;
-            if (r < a.M) {
-                const float* row = a.A + (size_t)r * a.tap_stride;
-                float s = 0.0f;
-                for (int k = lane; k < a.K; k += 64) s += row[k];
-                mean = hub_wave_sum(s) / (float)a.K;
-                float v = 0.0f;
-                for (int k = lane; k < a.K; k += 64) {
-                    const float d = row[k] - mean;
-                    v += d * d;
-                }
-                rstd = 1.0f / sqrtf(hub_wave_sum(v) / (float)a.K + a.eps);
-            }
+            if (r < a.M) ln_row_stats(a.A, nullptr, (size_t)r * a.tap_stride, a.K, a.eps, lane, &mean, &rstd);
             if (lane == 0) {
                 s_stat[rr][0] = mean;
                 s_stat[rr][1] = rstd;
@@ -142,8 +124,7 @@ __global__ __launch_bounds__(256) void k_hub_gemm(const HubGemm a) {
             for (int i = 0; i < 4; ++i) {
                 const int row = m0 + wr + rb * 16 + 4 * q + i;
                 if (row >= a.M) continue;
-                float y = acc[rb][cb][i] + bias;
-                if (a.act == HACT_GELU) y = hub_gelu(y);
+                float y = act_apply(acc[rb][cb][i] + bias, a.act);
                 const size_t o = (size_t)row * a.ldo + cg;
                 if (a.res) y += a.res[o];
                 a.out[o] = y;
@@ -160,19 +141,12 @@ __global__ __launch_bounds__(256) void k_hub_ln(const float* x, float* out, cons
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (r >= M) return;
     const float* row = x + (size_t)r * C;
-    float s = 0.0f;
-    for (int k = lane; k < C; k += 64) s += row[k];
-    const float mean = hub_wave_sum(s) / (float)C;
-    float v = 0.0f;
-    for (int k = lane; k < C; k += 64) {
-        const float d = row[k] - mean;
-        v += d * d;
-    }
-    const float rstd = 1.0f / sqrtf(hub_wave_sum(v) / (float)C + eps);
+    float mean, rstd;
+    ln_row_stats(row, nullptr, 0, C, eps, lane, &mean, &rstd);
     float* o = out + (size_t)r * C;
     for (int k = lane; k < C; k += 64) {
         const float y = (row[k] - mean) * rstd * gm[k] + be[k];
-        o[k] = act == HACT_GELU ? hub_gelu(y) : y;
+        o[k] = act_apply(y, act);
     }
 }
 hipError_t launch_hub_ln(const float* x, float* out, const float* gm, const float* be, int M, int C, float eps, int act, hipStream_t s) {
@@ -192,88 +166,6 @@ __global__ __launch_bounds__(256) void k_hub_conv0(const float* wave, long long 
     float acc = 0.0f;
     for (int jj = 0; jj < k; ++jj) acc = fmaf(w[c * k + jj], x[jj], acc);
     out[i] = acc + bias[c];
-}
-
-// ---- attention of one (clip, head, 16 queries): softmax(q k^T d^-1/2) v.  q | k | v are column blocks of one [rows][3 H] matrix.
-// Keys go by in chunks of HUB_KCH in index order with a running max m and sum l; the accumulator is rescaled by exp(m_old - m_new).
-__global__ __launch_bounds__(256) void k_hub_attn(const float* qkv, float* o, int T, int H, int d, float scale) {
-    __shared__ float s_q[16][68];
-    __shared__ float s_p[16][HUB_KCH];
-    __shared__ float s_m[16], s_l[16], s_alpha[16];
-    const int tid = threadIdx.x, h = blockIdx.y, b = blockIdx.z, q0 = blockIdx.x * 16;
-    const int ld = 3 * H;
-    const float* qb = qkv + (size_t)b * T * ld + h * d;
-    const float* kb = qb + H;
-    const float* vb = qb + 2 * H;
-    const int qi = tid >> 4, d4 = (tid & 15) * 4;
-    if (d4 < d) {
-        f32x4 x{0.0f, 0.0f, 0.0f, 0.0f};
-        if (q0 + qi < T) x = *reinterpret_cast<const f32x4*>(qb + (size_t)(q0 + qi) * ld + d4) * scale;
-        *reinterpret_cast<f32x4*>(&s_q[qi][d4]) = x;
-    }
-    if (tid < 16) {
-        s_m[tid] = -INFINITY;
-        s_l[tid] = 0.0f;
-    }
-    f32x4 acc{0.0f, 0.0f, 0.0f, 0.0f};
-    __syncthreads();
-    for (int k0 = 0; k0 < T; k0 += HUB_KCH) {
-        const int nk = min(HUB_KCH, T - k0);
-        {   // scores: thread = (key, group of 4 queries)
-            const int g = tid & 3;
-            for (int kj = tid >> 2; kj < nk; kj += 64) {
-                const float* kr = kb + (size_t)(k0 + kj) * ld;
-                float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-                for (int dd = 0; dd < d; dd += 4) {
-                    const f32x4 kv = *reinterpret_cast<const f32x4*>(kr + dd);
-                    const f32x4 q0v = *reinterpret_cast<const f32x4*>(&s_q[4 * g + 0][dd]), q1v = *reinterpret_cast<const f32x4*>(&s_q[4 * g + 1][dd]);
-                    const f32x4 q2v = *reinterpret_cast<const f32x4*>(&s_q[4 * g + 2][dd]), q3v = *reinterpret_cast<const f32x4*>(&s_q[4 * g + 3][dd]);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        s0 = fmaf(q0v[i], kv[i], s0);
-                        s1 = fmaf(q1v[i], kv[i], s1);
-                        s2 = fmaf(q2v[i], kv[i], s2);
-                        s3 = fmaf(q3v[i], kv[i], s3);
-                    }
-                }
-                s_p[4 * g + 0][kj] = s0;
-                s_p[4 * g + 1][kj] = s1;
-                s_p[4 * g + 2][kj] = s2;
-                s_p[4 * g + 3][kj] = s3;
-            }
-        }
-        __syncthreads();
-        {   // a wave per 4 rows: new running max, the chunk's exponentials, the running sum
-            const int wave = tid >> 6, lane = tid & 63;
-            for (int r = wave * 4; r < wave * 4 + 4; ++r) {
-                float m = -INFINITY;
-                for (int kj = lane; kj < nk; kj += 64) m = fmaxf(m, s_p[r][kj]);
-#pragma unroll
-                for (int of = 32; of > 0; of >>= 1) m = fmaxf(m, __shfl_xor(m, of, 64));
-                const float m_old = s_m[r], m_new = fmaxf(m_old, m);
-                float sum = 0.0f;
-                for (int kj = lane; kj < nk; kj += 64) {
-                    const float e = expf(s_p[r][kj] - m_new);
-                    s_p[r][kj] = e;
-                    sum += e;
-                }
-                sum = hub_wave_sum(sum);
-                if (lane == 0) {
-                    const float al = expf(m_old - m_new);      // (first chunk: exp(-inf) = 0)
-                    s_alpha[r] = al;
-                    s_l[r] = s_l[r] * al + sum;
-                    s_m[r] = m_new;
-                }
-            }
-        }
-        __syncthreads();
-        if (d4 < d) {
-            acc *= s_alpha[qi];
-            for (int kj = 0; kj < nk; ++kj) acc += *reinterpret_cast<const f32x4*>(vb + (size_t)(k0 + kj) * ld + d4) * s_p[qi][kj];
-        }
-        __syncthreads();
-    }
-    if (d4 < d && q0 + qi < T) *reinterpret_cast<f32x4*>(o + ((size_t)b * T + q0 + qi) * H + h * d + d4) = acc * (1.0f / s_l[qi]);
 }
 
 // ---- waveform normalisation: fixed-order reductions in fp64.  A pass writes HUB_PARTS partial sums; the next launch adds them up in index
@@ -333,10 +225,6 @@ __global__ __launch_bounds__(256) void k_hub_pos_scale(const float* v, const flo
     }
     s = hub_block_sum(s, s_red);
     if (threadIdx.x == 0) scale[tap] = g[tap] / (float)sqrt(s);
-}
-__global__ void k_hub_copy(const float* src, float* dst, long long n) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[i];
 }
 
 // =====================================================================================================================================
@@ -431,7 +319,7 @@ void hub_build(HubState* Sp, std::vector<Op>& ops, const float* wave, int n, int
             hipLaunchKernelGGL(k_hub_conv0, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, wave, (long long)n, w, bias, cur, T0, C, k, st, total);
             return hipGetLastError();
         });
-        add_ln("conv0.ln_gelu", cur, cur, pre + "layer_norm", B * T0, C, 1e-5f, HACT_GELU);
+        add_ln("conv0.ln_gelu", cur, cur, pre + "layer_norm", B * T0, C, 1e-5f, ACT_GELU);
     }
     for (int i = 1; i < S.nc; ++i) {
         const std::string pre = "feature_extractor.conv_layers." + std::to_string(i) + ".", tag = "conv" + std::to_string(i);
@@ -443,7 +331,7 @@ void hub_build(HubState* Sp, std::vector<Op>& ops, const float* wave, int n, int
         a.T_in = T[i - 1];
         a.T_out = T[i];
         add_gemm(tag, a);
-        add_ln(tag + ".ln_gelu", nxt, nxt, pre + "layer_norm", B * T[i], Co, 1e-5f, HACT_GELU);
+        add_ln(tag + ".ln_gelu", nxt, nxt, pre + "layer_norm", B * T[i], Co, 1e-5f, ACT_GELU);
         std::swap(cur, nxt);
     }
     S.last_feat = cur;
@@ -462,16 +350,13 @@ void hub_build(HubState* Sp, std::vector<Op>& ops, const float* wave, int n, int
     a.pad = f.pos_taps / 2;
     a.T_in = a.T_out = Tt;
     a.a_goff = S.Cg;
-    a.act = HACT_GELU;
+    a.act = ACT_GELU;
     a.res = S.P;
     add_gemm("pos_conv", a, f.pos_groups);
     auto add_keep = [&](const std::string& name, float* dst) {
         const float* src = S.X;
         const long long cnt = (long long)M * H;
-        add(name, 0.0, [=](hipStream_t s) {
-            hipLaunchKernelGGL(k_hub_copy, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, src, dst, cnt);
-            return hipGetLastError();
-        });
+        add(name, 0.0, [=](hipStream_t s) { return launch_tok_copy(src, 0, dst, 0, cnt, 1, s); });
     };
     if (S.keep) add_keep("keep.after_pos_conv", S.tap_pos);
     for (int l = 0; l < S.nl; ++l) {
@@ -481,16 +366,21 @@ void hub_build(HubState* Sp, std::vector<Op>& ops, const float* wave, int n, int
         a.ln_b = S.w.at(pre + "layer_norm.bias");
         a.eps = f.eps;
         add_gemm(tag + "qkv", a);
-        {
-            const float* qkv = S.QKV;
-            float* att = S.ATT;
-            const int heads = f.heads;
-            const float scale = 1.0f / std::sqrt((float)d);
-            add(tag + "attn", 4.0 * B * (double)Tt * Tt * H, [=](hipStream_t s) {
-                hipLaunchKernelGGL(k_hub_attn, dim3((unsigned)((Tt + 15) / 16), (unsigned)heads, (unsigned)B), dim3(256), 0, s, qkv, att, Tt, H, d, scale);
-                return hipGetLastError();
-            });
-        }
+        TokAttnArgs t{};
+        t.q = S.QKV;
+        t.k = S.QKV + H;
+        t.v = S.QKV + 2 * H;
+        t.o = S.ATT;
+        t.q_bs = t.k_bs = (long long)Tt * 3 * H;
+        t.q_rs = t.k_rs = 3 * H;
+        t.o_bs = (long long)Tt * H;
+        t.o_rs = H;
+        t.Lq = t.Lk = Tt;
+        t.H = f.heads;
+        t.d = d;
+        t.S = 1;
+        t.scale = 1.0f / std::sqrt((float)d);
+        add(tag + "attn", 4.0 * B * (double)Tt * Tt * H, [t, B](hipStream_t s) { return launch_tok_attn(t, B, HUB_KCH, s); });
         a = hub_linear(S.ATT, H, M, H, S.w.at(pre + "attention.out_proj.weight"), S.w.at(pre + "attention.out_proj.bias"), H, S.X, H);
         a.res = S.X;
         add_gemm(tag + "out_proj", a);
@@ -498,14 +388,14 @@ void hub_build(HubState* Sp, std::vector<Op>& ops, const float* wave, int n, int
         a.ln_g = S.w.at(pre + "final_layer_norm.weight");
         a.ln_b = S.w.at(pre + "final_layer_norm.bias");
         a.eps = f.eps;
-        a.act = HACT_GELU;
+        a.act = ACT_GELU;
         add_gemm(tag + "ff1", a);
         a = hub_linear(S.FFB, ffn, M, ffn, S.w.at(pre + "feed_forward.output_dense.weight"), S.w.at(pre + "feed_forward.output_dense.bias"), H, S.X, H);
         a.res = S.X;
         add_gemm(tag + "ff2", a);
         if (S.keep && l == 0) add_keep("keep.layer_0", S.tap_l0);
     }
-    add_ln("encoder.layer_norm", S.X, out, "encoder.layer_norm", M, H, f.eps, HACT_NONE);
+    add_ln("encoder.layer_norm", S.X, out, "encoder.layer_norm", M, H, f.eps, ACT_NONE);
 }
 
 // the argument checks of forward / num_launches / profile; nothing has been launched when they fail
@@ -668,11 +558,7 @@ int mtv_hubert_forward(mtv_ctx* c, const float* wave, int n_samples, int batch, 
     HIPCHK(hub_prepare(c, *S));
     std::vector<Op> ops;
     hub_build(S, ops, wave, n_samples, batch, T, out);
-    for (auto& op : ops) {
-        hipError_t e = op.run(s);
-        if (e != hipSuccess) return fail(MTV_ERR_HIP, "launch " + op.name + ": " + hipGetErrorString(e));
-    }
-    return MTV_OK;
+    return run_op_list(ops, s);
 }
 
 int mtv_hubert_num_launches(mtv_ctx* c, int n_samples, int batch, int* n_out) {
@@ -696,35 +582,7 @@ int mtv_hubert_profile(mtv_ctx* c, const float* wave, int n_samples, int batch, 
     HIPCHK(hub_prepare(c, *S));
     std::vector<Op> ops;
     hub_build(S, ops, wave, n_samples, batch, T, S->tap_l0);      // (the result lands in a scratch tensor)
-    const int n = (int)ops.size();
-    *n_out = n;
-    if (!out) return MTV_OK;
-    if (cap < n) return fail(MTV_ERR_INVALID, "profile table too small");
-    std::vector<hipEvent_t> ev((size_t)n + 1);
-    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-    std::vector<double> acc(n, 0.0);
-    for (int itr = 0; itr < iters; ++itr) {
-        HIPCHK(hipEventRecord(ev[0], s));
-        for (int i = 0; i < n; ++i) {
-            hipError_t e = ops[i].run(s);
-            if (e != hipSuccess) return fail(MTV_ERR_HIP, "launch " + ops[i].name + ": " + hipGetErrorString(e));
-            HIPCHK(hipEventRecord(ev[i + 1], s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-        for (int i = 0; i < n; ++i) {
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-            acc[i] += ms;
-        }
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    for (int i = 0; i < n; ++i) {
-        std::memset(&out[i], 0, sizeof(mtv_op_time));
-        std::strncpy(out[i].name, ops[i].name.c_str(), sizeof(out[i].name) - 1);
-        out[i].ms = (float)(acc[i] / iters);
-        out[i].flops = ops[i].flops;
-    }
-    return MTV_OK;
+    return profile_ops(c, ops, iters, out, cap, n_out, s);
 }
 
 int mtv_hubert_debug_keep(mtv_ctx* c, int keep) {

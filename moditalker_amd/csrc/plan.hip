@@ -1325,10 +1325,55 @@ static int get_plan(mtv_ctx* c, int B, int mode, Plan** out) {
     return MTV_OK;
 }
 
-int run_ops(mtv_ctx* c, Plan* p, hipStream_t s) {
-    for (auto& op : p->ops) {
+int run_op_list(std::vector<Op>& ops, hipStream_t s) {
+    for (auto& op : ops) {
         hipError_t e = op.run(s);
         if (e != hipSuccess) return fail(MTV_ERR_HIP, "launch " + op.name + ": " + hipGetErrorString(e));
+    }
+    return MTV_OK;
+}
+int run_ops(mtv_ctx* c, Plan* p, hipStream_t s) { return run_op_list(p->ops, s); }
+
+int profile_ops(mtv_ctx* c, std::vector<Op>& ops, int iters, mtv_op_time* out, int cap, int* n_out, hipStream_t s, const std::function<int()>& before_iter) {
+    if (iters < 1 || !n_out) return fail(MTV_ERR_INVALID, "bad argument");
+    const int n = (int)ops.size();
+    *n_out = n;
+    if (!out) return MTV_OK;
+    if (cap < n) return fail(MTV_ERR_INVALID, "profile table too small");
+    // one event between consecutive launches (n+1 in all): launch i is charged the interval between the
+    // event before it and the event after it, so the events' own cost is paid once per launch, not twice
+    struct Events {
+        std::vector<hipEvent_t> ev;
+        ~Events() {
+            for (auto e : ev)
+                if (e) (void)hipEventDestroy(e);
+        }
+    } evs{std::vector<hipEvent_t>((size_t)n + 1, nullptr)};
+    auto& ev = evs.ev;
+    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+    std::vector<double> acc(n, 0.0);
+    for (int it = 0; it < iters; ++it) {
+        int rc = before_iter ? before_iter() : MTV_OK;
+        if (rc != MTV_OK) return rc;
+        HIPCHK(hipEventRecord(ev[0], s));
+        for (int i = 0; i < n; ++i) {
+            hipError_t e = ops[i].run(s);
+            if (e != hipSuccess) return fail(MTV_ERR_HIP, "launch " + ops[i].name + ": " + hipGetErrorString(e));
+            HIPCHK(hipEventRecord(ev[i + 1], s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        for (int i = 0; i < n; ++i) {
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+            acc[i] += ms;
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        std::memset(&out[i], 0, sizeof(mtv_op_time));
+        std::strncpy(out[i].name, ops[i].name.c_str(), sizeof(out[i].name) - 1);
+        out[i].ms = (float)(acc[i] / iters);
+        out[i].flops = ops[i].flops;
+        out[i].bytes = ops[i].bytes;
     }
     return MTV_OK;
 }
@@ -1822,40 +1867,10 @@ static int profile_plan(mtv_ctx* c, int batch, int mode, int iters, mtv_op_time*
     Plan* p = nullptr;
     if ((rc = get_plan(c, batch, mode, &p)) != MTV_OK) return rc;
     if ((rc = autotune(c, p, s)) != MTV_OK) return rc;
-    const int n = (int)p->ops.size();
-    *n_out = n;
-    if (!out) return MTV_OK;
-    if (cap < n) return fail(MTV_ERR_INVALID, "profile table too small");
-    // one event between consecutive launches (n+1 in all): launch i is charged the interval between the
-    // event before it and the event after it, so the events' own cost is paid once per launch, not twice
-    std::vector<hipEvent_t> ev((size_t)n + 1);
-    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-    std::vector<double> acc(n, 0.0);
     const mtv_ddim_step one{500, 0, 1.0f, 0.0f, 1.0f, 0.0f, 0.0f, -1};    // a 1-entry step table for the step plan
-    for (int it = 0; it < iters; ++it) {
-        if (mode != MODE_FORWARD && (rc = sampler_setup(c, batch, nullptr, &one, 1, s)) != MTV_OK) return rc;
-        HIPCHK(hipEventRecord(ev[0], s));
-        for (int i = 0; i < n; ++i) {
-            hipError_t e = p->ops[i].run(s);
-            if (e != hipSuccess) return fail(MTV_ERR_HIP, "launch " + p->ops[i].name + ": " + hipGetErrorString(e));
-            HIPCHK(hipEventRecord(ev[i + 1], s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-        for (int i = 0; i < n; ++i) {
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-            acc[i] += ms;
-        }
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    for (int i = 0; i < n; ++i) {
-        std::memset(&out[i], 0, sizeof(mtv_op_time));
-        std::strncpy(out[i].name, p->ops[i].name.c_str(), sizeof(out[i].name) - 1);
-        out[i].ms = (float)(acc[i] / iters);
-        out[i].flops = p->ops[i].flops;
-        out[i].bytes = p->ops[i].bytes;
-    }
-    return MTV_OK;
+    std::function<int()> before;
+    if (mode != MODE_FORWARD) before = [&] { return sampler_setup(c, batch, nullptr, &one, 1, s); };
+    return profile_ops(c, p->ops, iters, out, cap, n_out, s, before);
 }
 
 int mtv_profile_forward(mtv_ctx* c, int batch, int iters, mtv_op_time* out, int cap, int* n_out, void* stream) {

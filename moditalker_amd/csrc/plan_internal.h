@@ -334,7 +334,12 @@ struct mtv_ctx {
 // ---- implemented in plan.hip, used by ae.hip ----
 int autotune(mtv_ctx* c, Plan* p, hipStream_t s);          // measured tile per conv shape (committed table first)
 int finish_split_k(mtv_ctx* c, Plan* p);                   // slab + arrival counters shared by the plan's split-K convs
+int run_op_list(std::vector<Op>& ops, hipStream_t s);      // every launch in order; fails with the name of the op that did
 int run_ops(mtv_ctx* c, Plan* p, hipStream_t s);
+// Per-launch times of an op list (mtv_profile_*, mtv_ae_profile, mtv_hubert_profile): `iters` runs with an event between consecutive
+// launches, the mean per launch into out[0 .. n).  out == nullptr: only *n_out.  before_iter (optional) runs ahead of every iteration.
+int profile_ops(mtv_ctx* c, std::vector<Op>& ops, int iters, mtv_op_time* out, int cap, int* n_out, hipStream_t s,
+                const std::function<int()>& before_iter = {});
 int capture(mtv_ctx* c, Plan* p, hipGraphExec_t* out);
 constexpr long X3_MIN_ROWS = 1024;
 bool x3_wanted(const PlanOptions& o, long rows);            // plan.hip: offer this conv to the split-bf16 kernels?
@@ -342,3 +347,19 @@ int check_ready(mtv_ctx* c, int batch);                     // (also refreshes t
 int ctx_init_common(mtv_ctx* c);
 int attach_win_pack(mtv_ctx* c, ConvOp* op);               // ConvArgs::Wwin for the k_conv_win tile an op runs on (opt.win_packed = 0: none)
 void force_family_tile(const PlanOptions& o, const ConvArgs& a, ConvTile* t);   // opt.force_win / _pw / _b3 / _lds
+
+// ---- implemented in tok_attn.hip, used by atom.hip and hubert.hip ----
+// softmax(q k^T scale) v of one head, 16 queries per workgroup.  Channels of a head are h d .. h d + d - 1 of the q, k and v rows; d is a
+// multiple of 4, at most 64.
+struct TokAttnArgs {
+    const float *q, *k, *v;
+    float* o;
+    long long q_bs, k_bs, o_bs;    // floats between clips
+    int q_rs, k_rs, o_rs;          // floats between tokens
+    int q_ss, k_ss, o_ss;          // floats between the interleaved streams of a clip (S = 2: lip | face rows of one token)
+    int Lq, Lk, H, d, S;
+    float scale;
+};
+hipError_t launch_tok_attn(const TokAttnArgs& a, int nb, int kch, hipStream_t s);      // kch: keys per chunk, 256 or 512; any Lk
+// dst[b][i] = src[b][i] for i < n, b < nb (strides in floats; src_bs = 0 broadcasts one block to every clip)
+hipError_t launch_tok_copy(const float* src, long long src_bs, float* dst, long long dst_bs, long long n, int nb, hipStream_t s);

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._context import HipContextMixin
 
 # The published config.json of facebook/hubert-large-ls960-ft, WRITTEN FROM MEMORY: the file cannot be fetched where this was
 # written.  Every value the forward depends on lives in this one dict; compare it with the checkpoint's own config.json
@@ -124,9 +125,11 @@ class _Encoder(nn.Module):
         self.layers = nn.ModuleList([_EncoderLayer(hidden, inter, eps) for _ in range(layers)])
 
 
-class HubertModel(nn.Module):
+class HubertModel(HipContextMixin, nn.Module):
     """HubertModel(**HUBERT_LARGE_CONFIG): transformers' HubertConfig keywords.  forward(input_values).last_hidden_state runs on
     the HIP library.  `max_samples` / `max_batch` size the workspace (a longer clip or larger batch rebuilds it)."""
+
+    _destroy = "mtv_hubert_destroy"
 
     def __init__(self, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
                  conv_dim=(512,) * 7, conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2), feat_extract_norm="group",
@@ -163,26 +166,6 @@ class HubertModel(nn.Module):
         self._key = None
         self._fingerprint = None
 
-    # ---- context life cycle (as the other classes)
-    def _release(self):
-        if getattr(self, "_ctx", None) is not None:
-            _lib.load().mtv_hubert_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def __getstate__(self):
-        st = dict(self.__dict__)
-        st["_ctx"], st["_key"], st["_fingerprint"] = None, None, None
-        return st
-
-    def invalidate_weights(self):
-        self._fingerprint = None
-
     def load_checkpoint_dict(self, sd, strict: bool = True):
         """load_state_dict for a published checkpoint's dict as it is (see convert_checkpoint_dict)."""
         sd = convert_checkpoint_dict(sd)
@@ -211,18 +194,9 @@ class HubertModel(nn.Module):
                 ctx = C.c_void_p()
                 _lib.check(lib.mtv_hubert_create(C.byref(cfg), C.byref(ctx)), "mtv_hubert_create")
             self._ctx, self._key, self._fingerprint = ctx, (device, cap_b, cap_n), None
-        fp = tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
+        fp = self._weights_fingerprint()
         if fp != self._fingerprint:
-            torch.cuda.synchronize(device)
-            sd = self.state_dict()
-            with torch.cuda.device(device):
-                key = C.create_string_buffer(256)
-                for i in range(lib.mtv_num_weights(self._ctx)):       # the context lists the keys its forward reads
-                    _lib.check(lib.mtv_weight_info(self._ctx, i, key, 256, None, None), "mtv_weight_info")
-                    k = key.value.decode()
-                    t = sd[k].detach().to(device="cpu", dtype=torch.float32).contiguous()
-                    shp = (C.c_int64 * t.dim())(*t.shape)
-                    _lib.check(lib.mtv_load_weight(self._ctx, k.encode(), C.c_void_p(t.data_ptr()), t.dim(), shp), f"mtv_load_weight({k})")
+            self._upload_weights(self._ctx, device)
             self._fingerprint = fp
         _lib.check(lib.mtv_hubert_debug_keep(self._ctx, int(self.debug_taps)), "mtv_hubert_debug_keep")
         return self._ctx

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._context import HipContextMixin
 
 
 def _zero(m: nn.Module) -> nn.Module:
@@ -51,10 +52,13 @@ class _Attn(nn.Module):
         self.proj_out = _zero(nn.Conv1d(ch, ch, 1))
 
 
-class UNetModel(nn.Module):
+class UNetModel(HipContextMixin, nn.Module):
     """Tri-plane UNet denoiser; constructor kwargs exactly as the reference YAML passes them
     (configs/latent-diffusion/base.yaml:27-38 -> unet.py:631-659), plus the geometry the reference
     hard-wires: `frames` (T, default 16; R is `image_size`)."""
+
+    _destroy = "mtv_destroy"
+    _transient = {"_ctx": None, "_ctx_device": None, "_ctx_batch": 0, "_fingerprint": None}
 
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks,
                  attention_resolutions, dropout=0, channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2,
@@ -172,27 +176,7 @@ class UNetModel(nn.Module):
         cfg.max_batch = max_batch
         return cfg
 
-    def _release(self):
-        if getattr(self, "_ctx", None) is not None:
-            _lib.load().mtv_destroy(self._ctx)       # (binds the context's own device before freeing)
-            self._ctx = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def _weights_fingerprint(self):
-        """(storage, version) of every parameter.  In-place writes through `.data` (p.data.copy_/lerp_: the usual
-        EMA / weight-surgery idiom) do NOT bump `_version`: call `invalidate_weights()` after such writes.
-        `load_state_dict` and `.to()/_apply` invalidate by themselves."""
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
-
-    def invalidate_weights(self):
-        """Force a re-upload of all weights to the HIP context before the next forward / sample."""
-        self._fingerprint = None
-
+    # (`load_state_dict` and `.to()/_apply` invalidate the weight fingerprint by themselves)
     def load_state_dict(self, *a, **k):
         r = super().load_state_dict(*a, **k)
         self.invalidate_weights()
@@ -202,13 +186,6 @@ class UNetModel(nn.Module):
         r = super()._apply(fn, *a, **k)
         self._fingerprint = None
         return r
-
-    # the library handle is process- and device-local: copies / pickles start without one and create their own
-    # lazily (the reference workflow deep-copies the model for its EMA twin, sample.py:226)
-    def __getstate__(self):
-        st = dict(self.__dict__)
-        st["_ctx"], st["_ctx_device"], st["_ctx_batch"], st["_fingerprint"] = None, None, 0, None
-        return st
 
     def __deepcopy__(self, memo):
         import copy
@@ -234,34 +211,9 @@ class UNetModel(nn.Module):
             lib.mtv_set_eager(self._ctx, int(self._eager))
         fp = self._weights_fingerprint()
         if fp != self._fingerprint:
-            self._upload_weights(device)
+            self._upload_weights(self._ctx, device)
             self._fingerprint = fp
         return self._ctx
-
-    def _upload_weights(self, device: torch.device):
-        lib = _lib.load()
-        sd = self.state_dict()
-        n = lib.mtv_num_weights(self._ctx)
-        key = C.create_string_buffer(256)
-        ndim = C.c_int()
-        shape = (C.c_int64 * 4)()
-        torch.cuda.synchronize(device)
-        for i in range(n):
-            _lib.check(lib.mtv_weight_info(self._ctx, i, key, 256, C.byref(ndim), shape), "mtv_weight_info")
-            k = key.value.decode()
-            if k not in sd:
-                raise _lib.MtvError(f"library expects weight '{k}' which this module does not hold")
-            t = sd[k].detach().to(device=device, dtype=torch.float32).contiguous()
-            if t.data_ptr() != sd[k].data_ptr():
-                # a converted / copied temporary is produced on torch's CURRENT stream, while mtv_load_weight copies and
-                # repacks on the NULL stream: finish producing it first (it stays referenced until the call returns,
-                # and the call returns only after its own copy + repack have run)
-                torch.cuda.current_stream(device).synchronize()
-            shp = (C.c_int64 * t.dim())(*t.shape)
-            _lib.check(lib.mtv_load_weight(self._ctx, k.encode(), C.c_void_p(t.data_ptr()), t.dim(), shp), f"mtv_load_weight({k})")
-        missing = lib.mtv_weights_missing(self._ctx)
-        if missing:
-            raise _lib.MtvError(f"{missing} weights missing after upload")
 
     def check_fault(self):
         """Raise MtvError if an in-launch hand-off of an earlier call on this module's context timed out (include/mtv_hip.h

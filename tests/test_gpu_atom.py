@@ -7,7 +7,7 @@ drift over the 50 steps is 1.0e-5, below the 1e-4 at which the bar would widen);
 
 Equalities asserted bit for bit, and why they must hold: every kernel of this path computes an output element from its own
 row and clip with a summation order fixed by the shapes of the weights (k_tok_linear: K chunks dealt to four waves, added
-in wave order; k_atom_attn: keys in index order), no atomics -- so neither a repeated call nor the batch size can change a bit."""
+in wave order; k_tok_attn: keys in index order), no atomics -- so neither a repeated call nor the batch size can change a bit."""
 import os
 
 import numpy as np

@@ -5,7 +5,7 @@ Every bar is read from the golden file: 10 x the max-abs difference between the 
 call (tests/golden/PIN_REPORT_hubert.txt lists them; 1.5e-5 .. 3.2e-5 on outputs of magnitude 2 .. 5).
 
 Equalities asserted bit for bit, and why they must hold: k_hub_gemm computes an output element from its own row, its column
-and the weights with K walked in index order by one wave; k_hub_ln and k_hub_attn work per row / per (clip, head, query
+and the weights with K walked in index order by one wave; k_hub_ln and k_tok_attn work per row / per (clip, head, query
 tile) with keys in index order; the normalisation adds fixed partial sums in index order.  No atomics anywhere, so neither
 a repeated call nor the batch size can change a bit."""
 import os

@@ -1,7 +1,7 @@
 """The HuBERT stage on the GPU (csrc/hubert.hip behind moditalker_amd.HubertModel) against the fp64 oracle (oracle/ref_hubert.py,
 pinned to transformers' outputs by tests/test_hubert_oracle_host.py) at the shapes the goldens cannot reach: k_hub_gemm's K / N
 / M tails as a Linear, as a conv whose 16-wide K chunk spans several taps, and as the positional conv (4-channel groups, an odd
-tap count, padding longer than the clip, three clips); k_hub_attn at head dims 4 / 20 / 64, on both sides of the 256-key chunk
+tap count, padding longer than the clip, three clips); k_tok_attn at head dims 4 / 20 / 64, on both sides of the 256-key chunk
 and with a peaked softmax; the waveform normalisation across its grid-stride wrap, in place and on a signal whose mean dwarfs
 its spread; a layer_norm_eps that differs from the conv layers' fixed 1e-5.
 
